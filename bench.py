@@ -5,7 +5,7 @@ fp32, random-init weights, everything inside the timed region that the reference
 (LA_BCP_train.py:235-270): teacher forward x2, pseudo-label + largest-CC x2, box draw, copy-paste mix x2,
 student forward x2, masked Dice+CE x2, backward, [gradient all-reduce when N>1], SGD, EMA.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload la|acdc|pancreas]
+  python bench.py [--gpus N --steps K --warmup W] [--workload la|acdc|pancreas] [--dump-outputs DIR]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 stdout's LAST line (rank 0) is ONE compact JSON record (< 4 KB, asserted): the contract keys only --
@@ -402,6 +402,56 @@ def cpu_baseline(workload, batch, labeled_bs, budget_s=45.0):
             "sec_per_step_all": [round(t, 3) for t in steady]}
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_MAX_BYTES = 64 * 10**6         # all files of one dump together
+DUMP_STATE_SAMPLE = 1 << 20         # entries kept of each network's state (parameters + BN running statistics) after the step
+
+
+def _host_array(t):
+    """a step result as a float32 (float64 when it is float64) host array; results are copied, so later passes cannot overwrite them"""
+    if isinstance(t, torch.Tensor):
+        t = t.detach()
+        return t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy().copy()
+    a = np.asarray(t)
+    return a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+
+
+def _seeded_sample(a, n, seed=0):
+    """a fixed sample of n entries of a (flattened): the same indices for the same size, whatever build computed a"""
+    a = a.reshape(-1)
+    if a.size <= n:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, n, replace=False))
+    return a[idx]
+
+
+def snapshot_outputs(r, models):
+    """what the timed path handed its caller in the last step -- the arrays of the step's result dict (losses, pseudo-labels, the student's
+    logits) -- plus a seeded sample of the student's and the teacher's state after its SGD / Adam and EMA updates.  Called right after the
+    timed region, before any further pass reuses the networks' buffers.  -> {name: array}, at most DUMP_MAX_BYTES in all"""
+    out = {k: _host_array(v) for k, v in (r.items() if isinstance(r, dict) else (("loss", r),))}
+    for name, m in zip(("model_state", "ema_state"), models):
+        sd = m.state_dict()
+        flat = torch.cat([sd[k].detach().reshape(-1).float().cpu() for k in sorted(sd) if sd[k].is_floating_point()]).numpy()
+        out[name + "_sample"] = _seeded_sample(flat, DUMP_STATE_SAMPLE)
+    rest, left = DUMP_MAX_BYTES, len(out)
+    for k in sorted(out, key=lambda k: out[k].nbytes):      # smallest first: an array larger than an even share of what is left is sampled
+        share = rest // left
+        if out[k].nbytes > share:
+            out[k] = _seeded_sample(out[k], share // out[k].itemsize, seed=1)
+        rest, left = rest - out[k].nbytes, left - 1
+    assert sum(a.nbytes for a in out.values()) <= DUMP_MAX_BYTES
+    return out
+
+
+def write_outputs(d, arrays):
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    print(f"[bench] outputs of the last timed step: {len(arrays)} arrays, {sum(a.nbytes for a in arrays.values()) / 1e6:.1f} MB -> {d}",
+          file=sys.stderr, flush=True)
+
+
 # ------------------------------------------------------------------------------------------------ workloads
 def make_workload(args, dp, dev):
     from bcp_amd import synth, train_step
@@ -488,6 +538,8 @@ def measure(args, dp, dev, cpu_budget_s=45.0, trim=False):
     dp.barrier()
     dt = time.perf_counter() - t0
     dt = dp.max_over_ranks(dt)
+    if getattr(args, "dump_outputs", None) and dp.rank == 0:
+        write_outputs(args.dump_outputs, snapshot_outputs(r, getattr(step, "models", ())))
     loss = float(r["loss"])
     assert np.isfinite(loss), "non-finite loss in the timed region"
     exposed = dp.exposed_ms_per_step(args.steps)
@@ -686,7 +738,12 @@ def main():
                     help="N > 1 ranks on ONE GPU (every rank uses cuda:0, gradient exchange over gloo: RCCL refuses two ranks per device): times "
                          "the bucketed exchange / overlap logic when no multi-GPU node is at hand -- NOT a scaling measurement")
     ap.add_argument("--no-extra", action="store_true", help="la, 1 GPU: skip the secondary lines (extra_workloads: acdc, pancreas; cpu_only: configs[0])")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0, the --workload line only): "
+                         "the same arguments give the same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch_size is None:
         args.batch_size = {"la": 4, "acdc": 24, "pancreas": 4}[args.workload]
     if args.labeled_bs is None:
@@ -790,6 +847,7 @@ def main():
             extra = {}
             for wl in ("acdc", "pancreas", "la_b8"):
                 a2 = copy.copy(args)
+                a2.dump_outputs = None
                 if wl == "la_b8":
                     # the reference's DEFAULT LA batch (LA_BCP_train.py:39-40: batch_size 8, labeled_bs 4; SURVEY 8d "also report"): GPU line only
                     a2.workload, a2.batch_size, a2.labeled_bs, a2.no_cpu_baseline = "la", 8, 4, True

@@ -4,7 +4,9 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -62,3 +64,27 @@ def test_record_minimal_and_multi_rank_and_failed_extra():
     back = _check(bench.compact_record(out), n1=False)
     assert back["ranks_seen"] == 2 and "kernels" not in back and "host_path" not in back["config"]
     assert len(back["extra_workloads"]["acdc"]["error"]) <= 120
+
+
+def test_dump_outputs_of_a_step():
+    """--dump-outputs: the step's result dict at the LA shapes (batch 4) plus samples of both networks' state, float32 / float64 host arrays
+    within the size budget, the same sample indices every time"""
+    g = torch.Generator().manual_seed(0)
+    r = {"loss": torch.tensor(0.5), "loss_l": torch.tensor(0.25, dtype=torch.float64),
+         "plab_a": (torch.rand(2, 112, 112, 80, generator=g) < 0.5).to(torch.uint8),
+         "plab_b": (torch.rand(2, 112, 112, 80, generator=g) < 0.5).to(torch.uint8),
+         "outputs_l": torch.randn(2, 2, 112, 112, 80, generator=g), "outputs_u": torch.randn(2, 2, 112, 112, 80, generator=g)}
+    big = torch.nn.Sequential(torch.nn.Linear(1024, 1536), torch.nn.BatchNorm1d(1536))       # more state than one sample holds
+    small = torch.nn.Linear(4, 3)
+    a = bench.snapshot_outputs(r, (big, small))
+    assert set(a) == set(r) | {"model_state_sample", "ema_state_sample"}
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_MAX_BYTES
+    assert a["loss_l"].dtype == np.float64 and all(v.dtype == np.float32 for k, v in a.items() if k != "loss_l")
+    assert float(a["loss"]) == 0.5 and a["outputs_l"].shape == (2, 2, 112, 112, 80)
+    assert np.array_equal(a["plab_a"], r["plab_a"].numpy().astype(np.float32))
+    assert a["model_state_sample"].size == bench.DUMP_STATE_SAMPLE and a["ema_state_sample"].size == 4 * 3 + 3
+    b = bench.snapshot_outputs(r, (big, small))
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    # an output larger than its share of the budget is kept as a fixed sample
+    huge = bench.snapshot_outputs({"x": torch.zeros(32 * 10**6)}, ())
+    assert huge["x"].nbytes <= bench.DUMP_MAX_BYTES

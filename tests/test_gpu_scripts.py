@@ -41,7 +41,8 @@ def test_scripts_with_device_input_pipeline(tmp_path, monkeypatch):
              "--augment", "--exp", "aug"])
 
 
-def test_pancreas_script(tmp_path):
+def test_pancreas_script(tmp_path, monkeypatch):
+    monkeypatch.chdir(tmp_path)         # the runs without --result_dir write under ./result/cutmix
     from bcp_amd.pancreas import train_pancreas as T
     T.main(["--pretraining_epochs", "1", "--self_training_epochs", "1", "--steps_per_epoch", "2", "--batch_size", "1"])
     # with the validation gate (pancreas/test_util.py:test_calculate_metric, sliding window over a 104x100x96 case) and the
