@@ -266,27 +266,23 @@ def check_mixloss(ops, dev, golden_dir):
 
 
 def _acdc_mix_loss_body(dice_loss, output, img_l, patch_l, mask, l_weight=1.0, u_weight=0.5, unlab=False):
-    """the reference's ACDC mix_loss BODY as its script writes it (ACDC_BCP_train.py:167-179; `dice_loss` is the module-level
-    `losses.DiceLoss(n_classes=4)` of :66) -- only the class behind `dice_loss` is ours"""
-    import torch.nn as nn
-    import torch.nn.functional as F
-    CE = nn.CrossEntropyLoss(reduction='none')
-    img_l, patch_l = img_l.type(torch.int64), patch_l.type(torch.int64)
-    output_soft = F.softmax(output, dim=1)
-    image_weight, patch_weight = l_weight, u_weight
-    if unlab:
-        image_weight, patch_weight = u_weight, l_weight
-    patch_mask = 1 - mask
-    loss_dice = dice_loss(output_soft, img_l.unsqueeze(1), mask.unsqueeze(1)) * image_weight
-    loss_dice += dice_loss(output_soft, patch_l.unsqueeze(1), patch_mask.unsqueeze(1)) * patch_weight
-    loss_ce = image_weight * (CE(output, img_l) * mask).sum() / (mask.sum() + 1e-16)
-    loss_ce += patch_weight * (CE(output, patch_l) * patch_mask).sum() / (patch_mask.sum() + 1e-16)
-    return loss_dice, loss_ce
+    """BCP's ACDC mixed loss, composed from the DiceLoss class under test (`dice_loss`) and a per-pixel cross-entropy: the image
+    labels count where `mask` is 1, the patch labels where it is 0; the two regions are weighted (l_weight, u_weight), swapped for
+    the unlabeled pair.  `mask` may be a dense tensor or a BCP_utils.BoxMask.  -> (Dice term, cross-entropy term)"""
+    probs = torch.softmax(output, dim=1)
+    w_in, w_out = (u_weight, l_weight) if unlab else (l_weight, u_weight)
+    dice_term, ce_term = 0.0, 0.0
+    for labels, region, wt in ((img_l, mask, w_in), (patch_l, 1 - mask, w_out)):
+        labels = labels.long()
+        dice_term = dice_term + wt * dice_loss(probs, labels.unsqueeze(1), region.unsqueeze(1))
+        per_pixel = F.cross_entropy(output, labels, reduction="none")
+        ce_term = ce_term + wt * (region * per_pixel).sum() / (region.sum() + 1e-16)
+    return dice_term, ce_term
 
 
 def check_diceloss_class(ops, dev, golden_dir):
-    """SURVEY 8b seam `utils.losses.DiceLoss(n)(inputs, target, mask=None, weight=None, softmax=False)`: (1) the reference's
-    ACDC mix_loss body run as written on top of it vs mixloss_acdc.npz (values 1e-5, gradient 1e-5 rel); (2) every keyword of
+    """SURVEY 8b seam `utils.losses.DiceLoss(n)(inputs, target, mask=None, weight=None, softmax=False)`: (1) BCP's
+    ACDC mixed loss composed on top of it (_acdc_mix_loss_body) vs mixloss_acdc.npz (values 1e-5, gradient 1e-5 rel); (2) every keyword of
     the class vs diceloss_class.npz (the reference's class, oracle/make_golden_dice.py); (3) layouts: NCHW-contiguous,
     channels-last and BoxMask inputs give the same numbers."""
     from bcp_amd.utils import BCP_utils as BU
