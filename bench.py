@@ -5,11 +5,16 @@ fp32, random-init weights, everything inside the timed region that the reference
 (LA_BCP_train.py:235-270): teacher forward x2, pseudo-label + largest-CC x2, box draw, copy-paste mix x2,
 student forward x2, masked Dice+CE x2, backward, [gradient all-reduce when N>1], SGD, EMA.
 
-  python bench.py [--gpus N --steps K --warmup W] [--workload la|acdc|pancreas] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--workload la|acdc|pancreas] [--dump-outputs DIR] [--full]
   N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: set-up (the two steps that record and capture the networks' passes), W warm-ups,
+the K timed steps, --dump-outputs, and the record.  --full then goes on, after the timed region, to everything else the benchmark
+measures: the per-op table and rooflines, the CPU baseline, the secondary workloads and the detail file.
 
 stdout's LAST line (rank 0) is ONE compact JSON record (< 4 KB, asserted): the contract keys only --
   metric value unit n_gpus steps warmup ms_per_step higher_is_better scaling vs_baseline dtype data config{workload, global_batch, parallelism}
+  (a plain run: these, ranks_seen, exposed_allreduce_ms_per_step when N > 1, and a roofline whose measured fields are null; the rest is --full's)
   roofline{bound, kernel, achieved, peak, unit, frac, traffic, ...}   the MFMA-bound op with the LARGEST share of the step (not a hand-picked
                 layer): `frac` from the mean duration of its recorded launches between two HIP events on its stream (agrees with the
                 rocprofv3 kernel trace of the same command, profiles/); `frac_in_step_bracket` = the same from an event pair around the op
@@ -509,8 +514,9 @@ def make_workload(args, dp, dev):
 
 
 def measure(args, dp, dev, cpu_budget_s=45.0, trim=False):
-    """one workload under the timing contract: W warm-ups, K timed steps between barrier + synchronize, max over ranks; then the
-    per-op table from profiled steps and (rank 0, N = 1) the CPU baseline.  -> the JSON object of the line (rank 0), None elsewhere"""
+    """one workload under the timing contract: W warm-ups, K timed steps between barrier + synchronize, max over ranks; then, with
+    --full, the host cost of a step, the per-op table from profiled steps and (rank 0, N = 1) the CPU baseline.  -> the JSON object of
+    the line (rank 0), None elsewhere"""
     from bcp_amd import plan
     step, info = make_workload(args, dp, dev)
     ranks_seen = dp.ranks_seen()
@@ -543,19 +549,21 @@ def measure(args, dp, dev, cpu_budget_s=45.0, trim=False):
     loss = float(r["loss"])
     assert np.isfinite(loss), "non-finite loss in the timed region"
     exposed = dp.exposed_ms_per_step(args.steps)
-    # host cost of ONE step with an empty queue (t_enq above includes back-pressure: once the host runs ahead, hipLaunchKernel
-    # blocks on the full queue and "enqueue time" just tracks the GPU)
-    host_one = []
-    for _ in range(5):
+    host_ms = None
+    if args.full:
+        # host cost of ONE step with an empty queue (t_enq above includes back-pressure: once the host runs ahead, hipLaunchKernel
+        # blocks on the full queue and "enqueue time" just tracks the GPU)
+        host_one = []
+        for _ in range(5):
+            torch.cuda.synchronize()
+            h0 = time.perf_counter()
+            step()
+            host_one.append(time.perf_counter() - h0)
         torch.cuda.synchronize()
-        h0 = time.perf_counter()
-        step()
-        host_one.append(time.perf_counter() - h0)
-    torch.cuda.synchronize()
-    host_ms = sorted(host_one)[len(host_one) // 2] * 1e3
+        host_ms = sorted(host_one)[len(host_one) // 2] * 1e3
 
     rows_top, rows_all, prof_ms = [], [], None
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         recs, prof_ms = profile_steps(step, args.profile_steps)
         rows_top, rows_all = op_table(recs, args.profile_steps, dt / args.steps * 1e3, top=8 if trim else 14)
         # second pass: the dominant op of each kind bracketed ALONE (every event is a marker packet between two kernels; with all ~300 ops
@@ -608,7 +616,7 @@ def measure(args, dp, dev, cpu_budget_s=45.0, trim=False):
     step_tflops = value * info["gflop_per_item"] / 1e3 / dp.world
     out = {
         "metric": info["metric"], "value": round(value, 3), "unit": info["unit"], "n_gpus": dp.world, "steps": args.steps, "warmup": args.warmup, "setup_steps": SETUP_STEPS,
-        "ms_per_step": round(ms, 3), "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3), "host_ms_per_step_empty_queue": round(host_ms, 3), "higher_is_better": True, "scaling": "weak",
+        "ms_per_step": round(ms, 3), "host_enqueue_ms_per_step": round(t_enq / args.steps * 1e3, 3), "host_ms_per_step_empty_queue": None if host_ms is None else round(host_ms, 3), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": DTYPE, "data": "synthetic",
         "config": {"workload": info["what"], "global_batch": global_batch, "parallelism": f"dp{dp.world}", "last_loss": round(loss, 6),
                    "host_path": (f"recorded network passes (bcp_amd/plan.py): forward = {'one HIP graph launch' if plan.GRAPHS >= 1 else 'per-launch replay from C'}, "
@@ -645,7 +653,7 @@ def measure(args, dp, dev, cpu_budget_s=45.0, trim=False):
     r0 = out["roofline"] or {}
     print(f"[bench] {args.workload} gpu: {value:.2f} {info['unit']}, {ms:.2f} ms/step (host enqueue {t_enq / args.steps * 1e3:.2f} ms/step), "
           f"dominant MFMA op {r0.get('kernel')} {r0.get('achieved')} TFLOP/s", file=sys.stderr, flush=True)
-    if dp.world == 1 and not args.no_cpu_baseline:
+    if args.full and dp.world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.workload, args.batch_size, args.labeled_bs, budget_s=cpu_budget_s)
     return out
 
@@ -727,17 +735,20 @@ def main():
                     help="la = BASELINE.json's metric (configs[1]); acdc / pancreas = the north_star's secondary lines (configs[3], [4])")
     ap.add_argument("--batch_size", type=int, default=None, help="per-GPU batch (la: 4 = configs[1]; acdc: 24 = configs[3]; pancreas: 4)")
     ap.add_argument("--labeled_bs", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-steps", type=int, default=3, help="steps run with per-op HIP events after the timed region (0: no kernels table)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the host cost of a step, the per-op table and rooflines, the CPU baseline and "
+                         "(la, 1 GPU) the secondary lines, and write bench_detail.json; a plain run only sets up, warms up, times and records")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--profile-steps", type=int, default=3, help="--full: steps run with per-op HIP events after the timed region (0: no kernels table)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="library tuning switch (bcp_set_option) for A/B measurements; the product defaults need none")
     ap.add_argument("--opt-late", action="append", default=[], metavar="NAME=VALUE",
                     help="MEASUREMENT ONLY: a library switch set after the first set-up step (the `whatif` bits: launches left out, results wrong)")
-    ap.add_argument("--no-roofline", action="store_true", help="same as --profile-steps 0 (A/B runs)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: same as --profile-steps 0 (A/B runs)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="N > 1 ranks on ONE GPU (every rank uses cuda:0, gradient exchange over gloo: RCCL refuses two ranks per device): times "
                          "the bucketed exchange / overlap logic when no multi-GPU node is at hand -- NOT a scaling measurement")
-    ap.add_argument("--no-extra", action="store_true", help="la, 1 GPU: skip the secondary lines (extra_workloads: acdc, pancreas; cpu_only: configs[0])")
+    ap.add_argument("--no-extra", action="store_true", help="--full, la, 1 GPU: skip the secondary lines (extra_workloads: acdc, pancreas; cpu_only: configs[0])")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB; rank 0, the --workload line only): "
                          "the same arguments give the same inputs, so two builds can be compared output for output")
@@ -840,7 +851,7 @@ def main():
         ops.set_option(k, v)
     out = measure(args, dp, dev)
     if dp.rank == 0:
-        if dp.world == 1 and args.workload == "la" and not args.no_extra:
+        if args.full and dp.world == 1 and args.workload == "la" and not args.no_extra:
             # the north_star's other single-GPU lines in the same driver-run record (same timing contract, own roofline + cpu_baseline),
             # bounded: fewer timed steps and a shorter CPU sample each
             import copy
@@ -868,7 +879,8 @@ def main():
                     out["cpu_only"] = {"error": f"{type(e).__name__}: {e}"}
         # the full report (per-op tables, both rooflines with their provenance, prose) goes to a FILE and to stderr; stdout's last line is
         # the compact record of the contract keys (round 5's 24.6 KB line did not survive the driver's stdout tail: BENCH_r05.json parsed = null)
-        detail_paths = write_detail(out)
+        # -- with --full only: a plain run leaves an earlier --full run's report as it was
+        detail_paths = write_detail(out) if args.full else []
         line = json.dumps(compact_record(out, detail=os.path.relpath(detail_paths[0], ROOT) if detail_paths else None), separators=(",", ":"))
         assert len(line) < MAX_LINE_BYTES, f"bench record is {len(line)} bytes (limit {MAX_LINE_BYTES})"
         sys.stderr.flush()

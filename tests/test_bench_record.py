@@ -1,5 +1,6 @@
 """bench.py's stdout record: compact, parseable, contract keys present (the 24.6 KB line of round 5 reached the driver as
 `parsed: null`).  CPU test: the record is built from canned `measure()` results -- the committed full report of round 5 and a minimal one."""
+import argparse
 import json
 import os
 import sys
@@ -88,3 +89,48 @@ def test_dump_outputs_of_a_step():
     # an output larger than its share of the budget is kept as a fixed sample
     huge = bench.snapshot_outputs({"x": torch.zeros(32 * 10**6)}, ())
     assert huge["x"].nbytes <= bench.DUMP_MAX_BYTES
+
+
+def _measure_counted(monkeypatch, **flags):
+    """bench.measure() with a stand-in workload whose steps are counted and the device calls stubbed out: -> (record, steps run, calls of the
+    measurements a plain run leaves to --full)"""
+    from bcp_amd.dp import DataParallel
+    n = {"step": 0, "profile_steps": 0, "cpu_baseline": 0}
+
+    def make_workload(args, dp, dev):
+        def step():
+            n["step"] += 1
+            return {"loss": torch.tensor(0.5)}
+        return step, {"metric": "m", "unit": "volumes/s", "what": "w", "gflop_per_item": 1.0}
+
+    def profile_steps(step, k, only=None):
+        n["profile_steps"] += 1
+        return [], 1.0
+
+    def cpu_baseline(*a, **k):
+        n["cpu_baseline"] += 1
+        return {"value": 1.0, "unit": "volumes/s", "cores": 1, "kind": "port", "sample": "s"}
+
+    monkeypatch.setattr(bench, "make_workload", make_workload)
+    monkeypatch.setattr(bench, "profile_steps", profile_steps)
+    monkeypatch.setattr(bench, "cpu_baseline", cpu_baseline)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a: None)
+    monkeypatch.setattr(torch.cuda, "empty_cache", lambda: None)
+    args = argparse.Namespace(workload="la", batch_size=4, labeled_bs=2, steps=7, warmup=3, profile_steps=3, no_cpu_baseline=False,
+                              dump_outputs=None, opt_late=[], full=False)
+    vars(args).update(flags)
+    out = bench.measure(args, DataParallel(), torch.device("cpu"))
+    return bench.compact_record(out), n.pop("step"), n
+
+
+def test_plain_run_does_only_the_set_up_warm_up_and_timed_steps(monkeypatch):
+    """a plain run: the two set-up steps, W warm-ups and K timed steps, nothing measured after them, the headline keys in the record"""
+    rec, steps, more = _measure_counted(monkeypatch)
+    assert steps == 2 + 3 + 7 and more == {"profile_steps": 0, "cpu_baseline": 0}
+    assert rec["steps"] == 7 and rec["warmup"] == 3 and rec["dtype"] == bench.DTYPE and rec["higher_is_better"] is True
+    assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "volumes/s"
+    assert "cpu_baseline" not in rec and rec["roofline"]["frac"] is None
+    # --full: the five empty-queue host steps, the profiled steps and the CPU baseline after the timed region
+    rec, steps, more = _measure_counted(monkeypatch, full=True)
+    assert steps == 2 + 3 + 7 + 5 and more == {"profile_steps": 1, "cpu_baseline": 1}
+    assert rec["cpu_baseline"]["value"] == 1.0
