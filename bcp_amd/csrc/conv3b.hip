@@ -854,10 +854,15 @@ __global__ __launch_bounds__(256) void k_c3p(const float* __restrict__ X, const 
 // waves run free and the matrix pipe always finds one with work; k_c3b synchronises its four waves after every tap pair (~0.35 us)
 // to hand the weight buffers over.  The pair loop is fully unrolled (compile-time tap offsets and register sets).
 // ------------------------------------------------------------------------------------------------
+// WL (persistent 16-channel instances on fp16 planes, one cin chunk): the chunk's TP x PL weight fragments are copied into the LDS once per
+// workgroup, in lane order (one conflict-free ds_read_b128 per fragment), behind the halo planes and the statistics scratch.  Streamed from
+// global memory, the next pair's weights shared the in-order vmcnt counter with the halo prefetch: the pair after it waited for the whole
+// next-tile halo to arrive from HBM (s_waitcnt vmcnt(2) two pairs behind the fetch).  Without global loads in the tap loop the prefetch
+// has the rest of the tile to land.  Same fragment values, same MFMA order: bit-identical to WL = false (option c3d16_form = 0).
 #ifndef BCP_C3D_ATTR
 #define BCP_C3D_ATTR
 #endif
-template <int KD, int TD, int TH, int TW, int NT, bool PER, bool BW = false, int PL = 3>
+template <int KD, int TD, int TH, int TW, int NT, bool PER, bool BW = false, int PL = 3, bool WL = false>
 __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restrict__ X, const float* __restrict__ Wp, const float* __restrict__ bias,
                                              float* __restrict__ Y, ConvDims cd, int n_tiles, int accumulate, StatsArg st) {
   using TL = Tile<KD, TD, TH, TW>;
@@ -866,12 +871,14 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   using HF = HaloFetch<TL>;
   using PP = Pipe<PL>;
   using frag_t = typename PP::frag;
+  static_assert(!WL || (PER && NT == 1 && !BW), "LDS-resident weights: the persistent one-n-tile instances");
 
   BCP_TS(0);
   BCP_TSR(59);
   HIP_DYNAMIC_SHARED(float4, smem4)
   unsigned short* Xb = reinterpret_cast<unsigned short*>(smem4);   // [PL][HV][XSB]
   double* Ss = reinterpret_cast<double*>(Xb + PL * XPLANE);        // [4][CT][2] statistics scratch
+  frag_t* Wf = reinterpret_cast<frag_t*>(Ss + 4 * CT * 2);         // WL: [TP][PL][64 lanes] weight fragments of the one cin chunk
 
   const int lane = threadIdx.x & 63;
   const int li = lane & 15, lg = lane >> 4, wave = threadIdx.x >> 6;
@@ -948,6 +955,11 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   const long long piece_stride = (long long)cd.Cout16 * 32;
   auto bload = [&](int cc, int tp, frag_t (&b)[NT][PL]) __attribute__((always_inline)) {
     if (B6_ABLATE & 4) return;
+    if constexpr (WL) {
+#pragma unroll
+      for (int s = 0; s < PL; ++s) b[0][s] = Wf[((tp < TP ? tp : TP - 1) * PL + s) * 64 + lane];
+      return;
+    }
     const unsigned short* p = Wl + ((long long)cc * TP + (tp < TP ? tp : TP - 1)) * PL * piece_stride;
 #pragma unroll
     for (int s = 0; s < PL; ++s)
@@ -982,10 +994,19 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
       for (int nt = 0; nt < NT; ++nt) { B0[nt][s] = *reinterpret_cast<const frag_t*>(Xb + s * 64 + nt * 8 + lane); B1[nt][s] = B0[nt][s]; }
   }
   BCP_TS(1);
+  if constexpr (WL) {
+    // (the launcher takes WL only for Cin16 == 16: c_begin = 0, one chunk)
+    const unsigned short* Wg = reinterpret_cast<const unsigned short*>(Wp + PP::pack_off(T, cd.Cin16, cd.Cout16)) + (long long)cout0 * 32;
+    for (int i = threadIdx.x; i < TP * PL * 64; i += 256) {
+      const int l = i & 63, f = i >> 6;
+      Wf[i] = *reinterpret_cast<const frag_t*>(Wg + (long long)f * piece_stride + (l & 15) * 32 + (l >> 4) * 8);
+    }
+  }
   hfetch_item(0);
-  bload(c_begin, 0, B0);
+  if (!WL) bload(c_begin, 0, B0);
   hstash();
   BCP_LDS_BARRIER();
+  if (WL) bload(c_begin, 0, B0);
   BCP_TS(2);
   // pair in front of which the next item's halo is fetched.  Round 3 (s_memtime stamps, tools/ts_probe.py, 32-channel level): with the
   // fetch four pairs ahead (TPE - 4) a chunk boundary cost ~9000 ticks against ~1000 per pair -- every workgroup of the launch
@@ -1726,21 +1747,30 @@ static int b6_launch(const float* X, const float* Wp, const float* bias, float* 
     if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>() && !PER) {
       if (bw) kd = k_c3d<KD, TD, TH, TW, NT, PER, true>;
     }
+    size_t lds_d = lds;
     if constexpr (b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
       if (use_f16) {
         kd = k_c3d<KD, TD, TH, TW, NT, PER, false, 2>;
         if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>() && !PER) {
           if (bw) kd = k_c3d<KD, TD, TH, TW, NT, PER, true, 2>;
         }
+        if constexpr (PER) {
+          // the weight fragments of the one cin chunk in the LDS (option c3d16_form): 14 pairs x 2 planes x 1 KB at the 3-D tile,
+          // 68 KB per workgroup with the halo planes -- still two workgroups per CU
+          if (options().c3d16_form != 0 && cd.Cin16 == 16 && sk == 1) {
+            kd = k_c3d<KD, TD, TH, TW, NT, PER, false, 2, true>;
+            lds_d += (size_t)((TL::T + 1) / 2) * 2 * 64 * 16;
+          }
+        }
       }
     }
-    hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
     if (sk == 1) {
-      hipLaunchKernelGGL(kd, dim3(P, gy, 1), dim3(256), lds, s, X, Wp, bias, Y, cd, gx, accumulate, sd);
+      hipLaunchKernelGGL(kd, dim3(P, gy, 1), dim3(256), lds_d, s, X, Wp, bias, Y, cd, gx, accumulate, sd);
     } else {
       const long long n = (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout;
       StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-      hipLaunchKernelGGL(kd, dim3(P, gy, sk), dim3(256), lds, s, X, Wp, (const float*)nullptr, ws, cd, gx, 0, none);
+      hipLaunchKernelGGL(kd, dim3(P, gy, sk), dim3(256), lds_d, s, X, Wp, (const float*)nullptr, ws, cd, gx, 0, none);
       hipLaunchKernelGGL(k_b6_sum_slabs, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, sk, n, cd.Cout, bias, Y,
                          accumulate);
     }
