@@ -40,6 +40,9 @@ for _name, _type, _default, _help in _BUILD_FLAGS:
     parser.add_argument("--" + _name, type=_type, default=_default, help=_help)
 parser.add_argument("--augment", action="store_true",
                     help="raw-size slices + the device-side RandomGenerator (rot90 / flip / rotate + zoom, dataloaders/dataset.py)")
+parser.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "contact"),
+                    help="the copy-paste region: box = one 2/3-side box (generate_mask, the reference's command line), random = 9 small boxes "
+                         "(ACDC_BCP_train.py:142 random_mask), contact = one full-width band (:156 contact_mask)")
 
 
 def patients_to_slices(dataset, patiens_num):
@@ -143,7 +146,8 @@ def pre_train(args, snapshot_path, device):
     iter_num = 0
     while iter_num < args.pre_iterations:
         for sampled in batches(db_train, sampler):
-            r = train_step.acdc_pre_train_step(model, optimizer, sampled["image"][:args.labeled_bs], sampled["label"][:args.labeled_bs])
+            r = train_step.acdc_pre_train_step(model, optimizer, sampled["image"][:args.labeled_bs], sampled["label"][:args.labeled_bs],
+                                               mask_strategy=train_step.cli_mask_strategy(args.mask_strategy))
             iter_num += 1
             _log(args, iter_num, r)
             keeper.maybe(iter_num, model, optimizer)
@@ -168,7 +172,7 @@ def self_train(args, pre_snapshot_path, snapshot_path, device):
     while iter_num < args.max_iterations:
         for sampled in batches(db_train, sampler):
             r = train_step.acdc_self_train_step(model, ema_model, optimizer, sampled["image"], sampled["label"], args.labeled_bs,
-                                                u_weight=args.u_weight, alpha=0.99)
+                                                u_weight=args.u_weight, alpha=0.99, mask_strategy=train_step.cli_mask_strategy(args.mask_strategy))
             iter_num += 1
             _log(args, iter_num, r)
             keeper.maybe(iter_num, model, optimizer)

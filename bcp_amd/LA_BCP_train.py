@@ -40,6 +40,9 @@ for _name, _type, _default in _REFERENCE_FLAGS:
     parser.add_argument("--" + _name, type=_type, default=_default)
 for _name, _type, _default, _help in _BUILD_FLAGS:
     parser.add_argument("--" + _name, type=_type, default=_default, help=_help)
+parser.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
+                    help="the copy-paste region: box = one 2/3-side box (context_mask, the reference's command line), random = 27 small boxes "
+                         "(utils/BCP_utils.py:30 random_mask), concat = one slab along z (:48 concate_mask)")
 parser.add_argument("--augment", action="store_true",
                     help="cases larger than the patch + the device-side RandomRotFlip / RandomCrop (dataloaders/dataset.py)")
 
@@ -145,7 +148,8 @@ def pre_train(args, snapshot_path, device):
     iter_num = 0
     while iter_num < args.pre_max_iteration:
         for sampled in batches(db_train, sampler):
-            r = train_step.la_pre_train_step(model, optimizer, sampled["image"][:args.labeled_bs], sampled["label"][:args.labeled_bs], args.mask_ratio)
+            r = train_step.la_pre_train_step(model, optimizer, sampled["image"][:args.labeled_bs], sampled["label"][:args.labeled_bs], args.mask_ratio,
+                                             mask_strategy=train_step.cli_mask_strategy(args.mask_strategy))
             iter_num += 1
             if iter_num % args.log_every == 0:
                 logging.info("iteration %d : loss: %03f, loss_dice: %03f, loss_ce: %03f" % (iter_num, float(r["loss"]), float(r["loss_dice"]), float(r["loss_ce"])))
@@ -174,7 +178,7 @@ def self_train(args, pre_snapshot_path, self_snapshot_path, device):
         for sampled in batches(db_train, sampler):
             get_current_consistency_weight(args, iter_num // 150)   # computed and logged only, as in the reference (:246)
             r = train_step.la_self_train_step(model, ema_model, optimizer, sampled["image"], sampled["label"], args.labeled_bs,
-                                              u_weight=args.u_weight, mask_ratio=args.mask_ratio, alpha=0.99)
+                                              u_weight=args.u_weight, mask_ratio=args.mask_ratio, alpha=0.99, mask_strategy=train_step.cli_mask_strategy(args.mask_strategy))
             iter_num += 1
             if iter_num % args.log_every == 0:
                 logging.info("iteration %d : loss: %03f, loss_l: %03f, loss_u: %03f" % (iter_num, float(r["loss"]), float(r["loss_l"]), float(r["loss_u"])))

@@ -14,7 +14,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libbcp_hip.so")
 
-ABI_VERSION = 511      # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
+ABI_VERSION = 512      # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
 
 P = C.c_void_p
 I = C.c_int
@@ -40,6 +40,8 @@ _SIGS = {
     "bcp_event_elapsed_ms": (I, [P, P, C.POINTER(F)]),
     "bcp_event_destroy": (I, [P]),
     "bcp_mix_box": (I, [P, P, P, I, I, I, I, I, P, P]),
+    "bcp_mask_boxes": (I, [P, I, I, I, I, P, I, I, P]),
+    "bcp_mix_mask": (I, [P, P, P, P, I, I, I, I, L, P]),
     "bcp_plabel_bin": (I, [P, P, L, F, P]),
     "bcp_plabel_argmax4": (I, [P, P, L, P]),
     "bcp_cc_workspace_bytes": (SZ, [I, I, I, I, I]),

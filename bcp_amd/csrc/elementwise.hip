@@ -14,6 +14,8 @@ __device__ __forceinline__ float rn_add(float a, float b) { return a + b; }
 
 namespace bcp {
 
+constexpr int kMaskBoxesMax = 32;  // bcp_mask_boxes: boxes per launch (the reference needs 27)
+
 static inline int stream_grid(long long n_items, int block) {
   long long g = (n_items + block - 1) / block;
   if (g > 2048) g = 2048;  // 256 CUs x 8 blocks, grid-stride the rest (guide G11)
@@ -90,6 +92,87 @@ __global__ __launch_bounds__(256) void k_mix_box_c1(const float* __restrict__ a,
         if ((w + 2 >= w0) & (w + 2 < w1)) v.z = vb.z;
         if ((w + 3 >= w0) & (w + 3 < w1)) v.w = vb.w;
       }
+    }
+    st4(out + (base + s) * 4, v);
+  }
+}
+
+// ---------------------------------------------------------------- region masks (union of boxes)
+// The reference's other copy-paste regions -- 27 small boxes (utils/BCP_utils.py:30-46 random_mask), 9 boxes (ACDC_BCP_train.py:142-154
+// random_mask), one slab / band (utils/BCP_utils.py:48-56 concate_mask, ACDC_BCP_train.py:156-164 contact_mask) -- as ONE uint8 map
+// [N][D][H][W], 0 inside the union and 1 elsewhere (the loss kernels' mask_or_null: 1 = image term).  The boxes travel by value.
+struct MaskBoxes {
+  int k;
+  int b[kMaskBoxesMax][6];  // d0, d1, h0, h1, w0, w1 (half-open, clamped to the volume by the launcher)
+};
+
+// one mask nibble (bit j = voxel j is inside the union) -> four mask bytes
+__device__ __forceinline__ unsigned mask_word(unsigned nib, unsigned flip) {
+  const unsigned in = (nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21);
+  return (in ^ flip) & 0x01010101u;
+}
+
+// Shaped like k_mix_box_c1: a workgroup row (blockIdx.y) is one (n, d) slice, so "does this box contain d" is workgroup-uniform and the
+// boxes that do not are skipped before any per-thread work.  A thread owns 16 voxels along W: it collects a 16-bit "inside" set over the
+// boxes and writes the 16 bytes with one vector store (V16), or as up to four 4-byte words where W % 16 != 0 (rows are then only 4-B aligned).
+template <bool V16>
+__global__ __launch_bounds__(256) void k_mask_boxes(uint8_t* __restrict__ out, int D, int H, int W, int W16 /* ceil(W / 16) */,
+                                                    MaskBoxes bx, unsigned flip /* 0x01010101: 1 outside; 0: complement */) {
+  const int slice = blockIdx.y;  // n * D + d
+  const int d = slice % D;
+  const long long base = (long long)slice * H * W;
+  const int items = H * W16;
+  for (int s = blockIdx.x * 256 + threadIdx.x; s < items; s += gridDim.x * 256) {
+    const int h = s / W16, w = (s - h * W16) * 16;
+    unsigned in = 0;
+    // chunks of eight boxes with compile-time indices: the boxes are kernel arguments, so each chunk arrives as a few wide scalar loads
+    // issued together, where a loop over a run-time index would wait for one scalar load per box (what of this is
+    // measured).  Slots past bx.k hold empty boxes (d0 == d1 == 0) and fail the first test.
+#pragma unroll
+    for (int k0 = 0; k0 < kMaskBoxesMax; k0 += 8) {
+      if (k0 >= bx.k) break;  // workgroup-uniform
+#pragma unroll
+      for (int k = k0; k < k0 + 8; ++k) {
+        if ((d < bx.b[k][0]) | (d >= bx.b[k][1])) continue;  // workgroup-uniform
+        if ((h < bx.b[k][2]) | (h >= bx.b[k][3])) continue;
+        int lo = bx.b[k][4] - w, hi = bx.b[k][5] - w;
+        lo = lo < 0 ? 0 : lo;
+        hi = hi > 16 ? 16 : hi;
+        if (lo < hi) in |= ((1u << hi) - 1u) & ~((1u << lo) - 1u);
+      }
+    }
+    uint8_t* p = out + base + (long long)h * W + w;
+    if (V16) {
+      uint4 v;
+      v.x = mask_word(in, flip);
+      v.y = mask_word(in >> 4, flip);
+      v.z = mask_word(in >> 8, flip);
+      v.w = mask_word(in >> 12, flip);
+      *reinterpret_cast<uint4*>(p) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (w + 4 * j < W) *reinterpret_cast<unsigned*>(p + 4 * j) = mask_word(in >> (4 * j), flip);  // W % 4 == 0: whole words only
+    }
+  }
+}
+
+// out = mask ? a : b per voxel, a select (values pass through bit for bit, NaN and -0.0 included -- as k_mix_box_c1 does).  blockIdx.y is
+// the sample; four mask bytes arrive as one 32-bit word per float4 and `b` is read only where one of them is zero: 4 (a) + 4 (out) + 1 (mask)
+// + 4 x zero fraction bytes per voxel.
+__global__ __launch_bounds__(256) void k_mix_mask(const float* __restrict__ a, const float* __restrict__ b, const uint8_t* __restrict__ mask,
+                                                  float* __restrict__ out, int V4 /* float4 per sample */, long long mask_sample_stride) {
+  const long long base = (long long)blockIdx.y * V4;
+  const unsigned* __restrict__ m = reinterpret_cast<const unsigned*>(mask + (long long)blockIdx.y * mask_sample_stride);
+  for (int s = blockIdx.x * 256 + threadIdx.x; s < V4; s += gridDim.x * 256) {
+    const unsigned mw = m[s];
+    float4 v = ld4(a + (base + s) * 4);
+    if ((mw - 0x01010101u) & ~mw & 0x80808080u) {  // some byte is zero
+      const float4 vb = ld4(b + (base + s) * 4);
+      if (!(mw & 0x000000ffu)) v.x = vb.x;
+      if (!(mw & 0x0000ff00u)) v.y = vb.y;
+      if (!(mw & 0x00ff0000u)) v.z = vb.z;
+      if (!(mw & 0xff000000u)) v.w = vb.w;
     }
     st4(out + (base + s) * 4, v);
   }
@@ -248,6 +331,61 @@ extern "C" int bcp_mix_box(const float* a, const float* b, float* out, int N, in
     hipLaunchKernelGGL(k_mix_box<4>, dim3(stream_grid((n_vec + 3) / 4, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, n_vec, D, H,
                        W, C, box6[0], box6[0] + box6[3], box6[1], box6[1] + box6[4], box6[2], box6[2] + box6[5]);
   BCP_CHECK_LAUNCH("bcp_mix_box");
+  return BCP_OK;
+}
+
+extern "C" int bcp_mask_boxes(uint8_t* out, int N, int D, int H, int W, const int* boxes, int K, int complement, void* stream) {
+  BCP_REQUIRE(out && (boxes || K == 0), "bcp_mask_boxes: null pointer");
+  BCP_REQUIRE(K >= 0 && K <= kMaskBoxesMax, "bcp_mask_boxes: %d boxes, at most %d travel as kernel arguments", K, kMaskBoxesMax);
+  BCP_REQUIRE(aligned16(out), "bcp_mask_boxes: out must be 16-B aligned");
+  BCP_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "bcp_mask_boxes: bad extents");
+  BCP_REQUIRE(W % 4 == 0, "bcp_mask_boxes: W must be a multiple of 4");
+  BCP_REQUIRE((long long)N * D <= 65535 && (long long)N * D * H * W < (1LL << 31), "bcp_mask_boxes: tensor too large");
+  MaskBoxes bx{};
+  const int ext[3] = {D, H, W};
+  for (int k = 0; k < K; ++k) {
+    const int* b = boxes + 6 * k;
+    BCP_REQUIRE(b[3] >= 0 && b[4] >= 0 && b[5] >= 0, "bcp_mask_boxes: box %d has a negative size", k);
+    bool empty = false;
+    int lim[6];
+    for (int ax = 0; ax < 3; ++ax) {  // clamp [start, start + size) to [0, extent)
+      const long long lo = b[ax] < 0 ? 0 : b[ax], hi = (long long)b[ax] + b[3 + ax] > ext[ax] ? ext[ax] : (long long)b[ax] + b[3 + ax];
+      lim[2 * ax] = (int)(lo > ext[ax] ? ext[ax] : lo);
+      lim[2 * ax + 1] = (int)hi;
+      empty |= lim[2 * ax] >= lim[2 * ax + 1];
+    }
+    if (empty) continue;
+    for (int j = 0; j < 6; ++j) bx.b[bx.k][j] = lim[j];
+    ++bx.k;
+  }
+  const int W16 = (W + 15) / 16;
+  const long long items = (long long)H * W16;
+  const int gx = (int)((items + 255) / 256 > 64 ? 64 : (items + 255) / 256);
+  const unsigned flip = complement ? 0u : 0x01010101u;
+  if (W % 16 == 0)
+    hipLaunchKernelGGL(k_mask_boxes<true>, dim3(gx, N * D), dim3(256), 0, (hipStream_t)stream, out, D, H, W, W16, bx, flip);
+  else
+    hipLaunchKernelGGL(k_mask_boxes<false>, dim3(gx, N * D), dim3(256), 0, (hipStream_t)stream, out, D, H, W, W16, bx, flip);
+  BCP_CHECK_LAUNCH("bcp_mask_boxes");
+  return BCP_OK;
+}
+
+extern "C" int bcp_mix_mask(const float* a, const float* b, const uint8_t* mask, float* out, int N, int D, int H, int W,
+                            long long mask_sample_stride, void* stream) {
+  BCP_REQUIRE(a && b && mask && out, "bcp_mix_mask: null pointer");
+  BCP_REQUIRE(aligned16(a) && aligned16(b) && aligned16(out), "bcp_mix_mask: pointers must be 16-B aligned");
+  BCP_REQUIRE((reinterpret_cast<uintptr_t>(mask) & 3u) == 0, "bcp_mix_mask: mask must be 4-B aligned");
+  BCP_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0, "bcp_mix_mask: bad extents");
+  BCP_REQUIRE(W % 4 == 0, "bcp_mix_mask: W must be a multiple of 4");
+  const long long V = (long long)D * H * W, n_vec = (long long)N * V / 4;
+  BCP_REQUIRE(n_vec < (1LL << 29) && N <= 65535, "bcp_mix_mask: tensor too large (>= 2^31 floats)");
+  BCP_REQUIRE(mask_sample_stride == 0 || (mask_sample_stride >= V && mask_sample_stride % 4 == 0),
+              "bcp_mix_mask: mask_sample_stride must be 0 (one map for all samples) or a multiple of 4 >= D*H*W");
+  const long long V4 = V / 4;
+  long long gx = (V4 + 255) / 256, cap = (2048 + N - 1) / N;      // ~8 workgroups per CU over the whole launch, grid-stride the rest
+  if (gx > cap) gx = cap;
+  hipLaunchKernelGGL(k_mix_mask, dim3((int)gx, N), dim3(256), 0, (hipStream_t)stream, a, b, mask, out, (int)V4, mask_sample_stride);
+  BCP_CHECK_LAUNCH("bcp_mix_mask");
   return BCP_OK;
 }
 

@@ -235,6 +235,32 @@ class Ops:
         self.b.call("bcp_mix_box", _p(a), _p(b), _p(out), N, D, H, W, Cc, self.box_arg(box6), self.stream(a))
         return out
 
+    def mask_boxes(self, boxes, shape, device, complement=False, out=None):
+        """uint8 [N,D,H,W] map: 0 inside the union of `boxes` (each a box6), 1 elsewhere (complement: swapped); every sample the same."""
+        N, D, H, W = (int(v) for v in shape)
+        flat = [int(v) for b in boxes for v in b]
+        if len(flat) != 6 * len(boxes):
+            raise _lib.BcpError("mask_boxes: every box is six integers (d, h, w, size_d, size_h, size_w)")
+        if out is None:
+            out = torch.empty((N, D, H, W), dtype=torch.uint8, device=device)
+        self._chk(out)
+        arr = (C.c_int * max(len(flat), 1))(*flat)
+        self.b.call("bcp_mask_boxes", _p(out), N, D, H, W, arr, len(boxes), int(bool(complement)), self.stream(out))
+        return out
+
+    def mix_mask(self, a, b, mask, out=None):
+        """out = mask ? a : b (a select: values pass through bit for bit).  a, b: [N,D,H,W,1] float32; mask: uint8 [D,H,W] (one map for all
+        samples) or [N,D,H,W]."""
+        self._chk(a, b, mask)
+        N, D, H, W, Cc = a.shape
+        if Cc != 1 or mask.dtype != torch.uint8 or tuple(mask.shape[-3:]) != (D, H, W) or mask.numel() not in (D * H * W, N * D * H * W):
+            raise _lib.BcpError("mix_mask: single-channel images and a uint8 [D,H,W] or [N,D,H,W] mask")
+        if out is None:
+            out = torch.empty_like(a)
+        stride = 0 if mask.numel() == D * H * W else D * H * W
+        self.b.call("bcp_mix_mask", _p(a), _p(b), _p(mask), _p(out), N, D, H, W, stride, self.stream(a))
+        return out
+
     def plabel_bin(self, logits, thres=0.5):
         self._chk(logits)
         N, D, H, W, Cc = logits.shape

@@ -62,17 +62,18 @@ class _LoaderStreams:
         return st
 
 
-def pretrain(net1, optimizer, streams, steps):
-    """train_pancreas.py:50-101: copy-paste of the two labeled streams, supervised (CE + Dice) / 2"""
+def pretrain(net1, optimizer, streams, steps, mask_strategy=None):
+    """train_pancreas.py:50-101: copy-paste of the two labeled streams, supervised (CE + Dice) / 2.  mask_strategy: None = the reference's
+    64^3 box, "random" / "concat" = the region of utils/BCP_utils.py random_mask / concate_mask"""
     net1.train()
     for _ in range(steps):
         st = streams() if callable(streams) else streams
         vols, labs = torch.cat([st[0][0], st[1][0]]), torch.cat([st[0][1], st[1][1]])
-        r = train_step.la_pre_train_step(net1, optimizer, vols, labs, variant="pancreas")
+        r = train_step.la_pre_train_step(net1, optimizer, vols, labs, variant="pancreas", mask_strategy=mask_strategy)
     return r["loss"]
 
 
-def ema_cutmix(net, ema_net, optimizer, streams, steps, dp=None, grouped=None):
+def ema_cutmix(net, ema_net, optimizer, streams, steps, dp=None, grouped=None, mask_strategy=None):
     """train_pancreas.py:103-179 through train_step.la_self_train_step(variant='pancreas').  grouped (default: whenever the four
     streams are views of one resident batch): the two teacher calls and the two student calls of an iteration are launched as one
     grouped forward each -- InstanceNorm statistics are per sample, so this is the same arithmetic in half the launches;
@@ -88,7 +89,7 @@ def ema_cutmix(net, ema_net, optimizer, streams, steps, dp=None, grouped=None):
         else:
             vols, labs, bs = torch.cat([s_[0] for s_ in st]), torch.cat([s_[1] for s_ in st]), st[0][0].shape[0]
         r = train_step.la_self_train_step(net, ema_net, optimizer, vols, labs, 2 * bs, variant="pancreas", connect_mode=connect_mode,
-                                          alpha=alpha, dp=dp, grouped=grouped)
+                                          alpha=alpha, dp=dp, grouped=grouped, mask_strategy=mask_strategy)
     return r["loss"]
 
 
@@ -115,7 +116,10 @@ def main(argv=None):
     ap.add_argument("--list_dir", type=str, default="", help="directory holding <split_name>/<10|20>percent/{train_lab,train_unlab,test}.txt (the reference hard-codes its own, pancreas/dataloaders.py:103-106)")
     ap.add_argument("--labelp", type=int, default=10)
     ap.add_argument("--device_input_pipeline", type=int, default=0, help="1: draw every batch from the four loader streams of the reference (RandomCrop / CenterCrop to 96^3, pancreas/dataloaders.py) with the crops done on the device")
+    ap.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
+                    help="the copy-paste region: box = one 64^3 box (the reference's loop), random = 27 small boxes, concat = one slab along z (utils/BCP_utils.py:30-56)")
     args = ap.parse_args(argv)
+    strategy = train_step.cli_mask_strategy(args.mask_strategy)
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     np.random.seed(seed_test)
     torch.manual_seed(seed_test)
@@ -147,7 +151,7 @@ def main(argv=None):
                 save_net_opt(net, optimizer, best_pre, ep)
                 max_dice = val_dice
             logging.info("Evaluation: val_dice: %.4f, val_maxdice: %.4f", val_dice, max_dice)
-        loss = pretrain(net, optimizer, streams, args.steps_per_epoch)
+        loss = pretrain(net, optimizer, streams, args.steps_per_epoch, mask_strategy=strategy)
         logging.info("pretrain epoch %d loss %f", ep, float(loss.detach()))
     if val is not None and best_pre.exists():                         # :115-117 -- both nets start from the best pre-trained state
         load_net_opt(net, optimizer, best_pre)
@@ -162,7 +166,7 @@ def main(argv=None):
                 save_net(net, st_dir / f"best_ema_{label_percent}_self.pth")
                 max_dice = val_dice
             logging.info("Evaluation: val_dice: %.4f, val_maxdice: %.4f", val_dice, max_dice)
-        loss = ema_cutmix(net, ema_net, optimizer, streams, args.steps_per_epoch)
+        loss = ema_cutmix(net, ema_net, optimizer, streams, args.steps_per_epoch, mask_strategy=strategy)
         logging.info("self-train epoch %d loss %f", ep, float(loss.detach()))
 
 

@@ -211,6 +211,41 @@ class FlatAdam:
                 self.steps = max(self.steps, int(float(e["step"])))
 
 
+# ------------------------------------------------------------------------------------------ masking strategies
+# The paper's ablation of the copy-paste region: None = the default one box (context_mask / generate_mask; pancreas: a 64^3 box), "random" =
+# many small boxes on a grid, "concat" (3-D) / "contact" (2-D) = one full-width slab.  The non-default ones come back as BU.RegionMask.
+def _check_strategy(mask_strategy, allowed):
+    if mask_strategy is not None and mask_strategy not in allowed:
+        raise ValueError(f"mask_strategy {mask_strategy!r}: this step knows None (the default box) and {', '.join(repr(a) for a in allowed)}")
+
+
+def cli_mask_strategy(value):
+    """the drivers' --mask_strategy value -> the step functions' keyword ("box", the default region, is None there)"""
+    return None if value == "box" else value
+
+
+def _draw_3d(mask_strategy, img):
+    return BU.random_mask(img) if mask_strategy == "random" else BU.concate_mask(img)
+
+
+def _draw_2d(mask_strategy, img):
+    return random_mask(img) if mask_strategy == "random" else contact_mask(img)
+
+
+def _explicit_masks(box, spatial, batch, device):
+    """the `box=` parity hook: one box -> BoxMask pair; a list of boxes -> RegionMask pair"""
+    if len(box) and isinstance(box[0], (tuple, list)):
+        return BU._region_pair(box, spatial, batch, device)
+    return BU.BoxMask(box, spatial, None, False, device), BU.BoxMask(box, spatial, batch, False, device)
+
+
+def _rasterise_early(loss_mask, like, n):
+    """grouped steps: a multi-box region's one rasterise launch goes in front of the mix (under the teacher's pass), so that the loss finds the
+    map ready -- nothing is added between the student's forward and backward pass"""
+    if isinstance(loss_mask, BU.RegionMask) and not loss_mask.single():
+        loss_mask.u8(_ops_for(like), n, like.device)
+
+
 # ------------------------------------------------------------------------------------------ LA / pancreas step
 class _NoVolatileIO:
     """the unfused loops (grouped=False: the reference's four separate network calls) hold the first call's outputs across the second call
@@ -230,23 +265,25 @@ class _NoVolatileIO:
 
 def la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box=None, drops=None,
                        u_weight=0.5, mask_ratio=2 / 3, alpha=0.99, variant="la", connect_mode=None, dp=None, grouped=True,
-                       overlap=True, plabs=None):
+                       overlap=True, plabs=None, mask_strategy=None):
+    _check_strategy(mask_strategy, ("random", "concat"))
     if not grouped and (getattr(model, "volatile_io", False) or getattr(ema_model, "volatile_io", False)):
         with _NoVolatileIO(model, ema_model):
             return la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box, drops, u_weight, mask_ratio, alpha,
-                                      variant, connect_mode, dp, grouped, overlap, plabs)
+                                      variant, connect_mode, dp, grouped, overlap, plabs, mask_strategy)
     return _la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box, drops, u_weight, mask_ratio, alpha, variant,
-                               connect_mode, dp, grouped, overlap, plabs)
+                               connect_mode, dp, grouped, overlap, plabs, mask_strategy)
 
 
 def _la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box=None, drops=None,
                         u_weight=0.5, mask_ratio=2 / 3, alpha=0.99, variant="la", connect_mode=None, dp=None, grouped=True,
-                        overlap=True, plabs=None):
+                        overlap=True, plabs=None, mask_strategy=None):
     """One self-training iteration, LA_BCP_train.py:235-270 (variant 'pancreas': train_pancreas.py:145-171).
 
     volume_batch [B,1,X,Y,Z] float32 laid out lab_a|lab_b|unlab_a|unlab_b, label_batch [B,X,Y,Z].
-    box: explicit (w,h,z,pw,ph,pz) for parity runs, else drawn by context_mask from np.random as the
-    reference does.  drops: optional injected Dropout3d keep-masks {'t_a','t_b','s_l','s_u'}.
+    box: explicit (w,h,z,pw,ph,pz) for parity runs -- or a list of such boxes, their union -- else drawn from np.random as the
+    reference does: by context_mask (pancreas: generate_mask), or with mask_strategy "random" / "concat" by BU.random_mask /
+    BU.concate_mask (utils/BCP_utils.py:30-56).  drops: optional injected Dropout3d keep-masks {'t_a','t_b','s_l','s_u'}.
     plabs: parity hook like `box` / `drops` -- (plab_a, plab_b) uint8 pseudo-labels the student is trained on INSTEAD of the
     teacher's (which are still computed and returned as 'plab_a' / 'plab_b'): takes the discrete pseudo-label bifurcations out
     of a multi-step comparison (tests/net_checks.py:check_la_traj5).
@@ -291,16 +328,17 @@ def _la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, 
             unoutput_b = ema_model(unimg_b, features=False)[0]
             plab_a = get_cut_mask(unoutput_a, nms=1, connect_mode=connect_mode)
             plab_b = get_cut_mask(unoutput_b, nms=1, connect_mode=connect_mode)
-        if box is None:
-            if variant == "la":
-                img_mask, loss_mask = BU.context_mask(img_a, mask_ratio)
-            else:
-                from .pancreas.pancreas_utils import generate_mask
-                img_mask, loss_mask = generate_mask(img_a, 64)
+        if box is not None:
+            img_mask, loss_mask = _explicit_masks(box, tuple(volume_batch.shape[2:]), sub_bs, volume_batch.device)
+        elif mask_strategy is not None:
+            img_mask, loss_mask = _draw_3d(mask_strategy, img_a)
+        elif variant == "la":
+            img_mask, loss_mask = BU.context_mask(img_a, mask_ratio)
         else:
-            sp = tuple(volume_batch.shape[2:])
-            img_mask = BU.BoxMask(box, sp, None, False, volume_batch.device)
-            loss_mask = BU.BoxMask(box, sp, sub_bs, False, volume_batch.device)
+            from .pancreas.pancreas_utils import generate_mask
+            img_mask, loss_mask = generate_mask(img_a, 64)
+        if grouped:
+            _rasterise_early(loss_mask, volume_batch, sub_bs)
     own_plabs = (plab_a, plab_b)
     if plabs is not None:
         plab_a, plab_b = plabs[0].to(volume_batch.device), plabs[1].to(volume_batch.device)
@@ -369,22 +407,25 @@ def _la_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, 
                 outputs_l=outputs_l.detach(), outputs_u=outputs_u.detach())
 
 
-def la_pre_train_step(model, optimizer, volume_batch, label_batch, mask_ratio=2 / 3, box=None, variant="la"):
+def la_pre_train_step(model, optimizer, volume_batch, label_batch, mask_ratio=2 / 3, box=None, variant="la", mask_strategy=None):
     """One pre-training iteration, LA_BCP_train.py:150-167 (variant 'pancreas': train_pancreas.py:83-97, a 64^3 box): the two
     halves of the LABELED batch are copy-pasted into each other (images and labels alike), the loss is the supervised
-    (CE + Dice) / 2.  Returns device scalars."""
+    (CE + Dice) / 2.  box / mask_strategy: as la_self_train_step.  Returns device scalars."""
     from .utils.losses import sup_loss_parts
+    _check_strategy(mask_strategy, ("random", "concat"))
     sub_bs = volume_batch.shape[0] // 2
     img_a, img_b = volume_batch[:sub_bs], volume_batch[sub_bs:2 * sub_bs]
     lab_a, lab_b = label_batch[:sub_bs], label_batch[sub_bs:2 * sub_bs]
     with torch.no_grad():
-        if box is None and variant == "pancreas":
+        if box is not None:
+            img_mask, _ = _explicit_masks(box, tuple(volume_batch.shape[2:]), sub_bs, volume_batch.device)
+        elif mask_strategy is not None:
+            img_mask, _ = _draw_3d(mask_strategy, img_a)
+        elif variant == "pancreas":
             from .pancreas.pancreas_utils import generate_mask as pancreas_mask
             img_mask, _ = pancreas_mask(img_a, 64)
-        elif box is None:
-            img_mask, _ = BU.context_mask(img_a, mask_ratio)
         else:
-            img_mask = BU.BoxMask(box, tuple(volume_batch.shape[2:]), None, False, volume_batch.device)
+            img_mask, _ = BU.context_mask(img_a, mask_ratio)
     mixed_img = img_a * img_mask + img_b * (1 - img_mask)
     mixed_lab = lab_a * img_mask + lab_b * (1 - img_mask)
     outputs = model(mixed_img, features=False)[0]
@@ -407,6 +448,30 @@ def generate_mask(img):
     return BU.BoxMask(box, (img_x, img_y), None, False, img.device), BU.BoxMask(box, (img_x, img_y), batch_size, False, img.device)
 
 
+def random_mask(img, shrink_param=3):
+    """ACDC_BCP_train.py:142-154: shrink_param^2 zero boxes, one per cell of a shrink_param x shrink_param grid; two np.random.randint
+    draws per cell (w then h), cells in x_s, y_s order"""
+    batch_size, channel, img_x, img_y = img.shape[0], img.shape[1], img.shape[2], img.shape[3]
+    x_split, y_split = int(img_x / shrink_param), int(img_y / shrink_param)
+    patch_x, patch_y = int(img_x * 2 / (3 * shrink_param)), int(img_y * 2 / (3 * shrink_param))
+    boxes = []
+    for x_s in range(shrink_param):
+        for y_s in range(shrink_param):
+            w = np.random.randint(x_s * x_split, (x_s + 1) * x_split - patch_x)
+            h = np.random.randint(y_s * y_split, (y_s + 1) * y_split - patch_y)
+            boxes.append((w, h, patch_x, patch_y))
+    return BU._region_pair(boxes, (img_x, img_y), batch_size, img.device)
+
+
+def contact_mask(img):
+    """ACDC_BCP_train.py:156-164: one full-width zero band, one np.random.randint draw.  As the reference writes it, the band runs along the
+    FIRST image axis while its length and the draw's bound come from the second (the two agree for square slices)"""
+    batch_size, channel, img_x, img_y = img.shape[0], img.shape[1], img.shape[2], img.shape[3]
+    patch_y = int(img_y * 4 / 9)
+    h = np.random.randint(0, img_y - patch_y)
+    return BU._region_pair([(h, 0, patch_y, img_y)], (img_x, img_y), batch_size, img.device)
+
+
 def acdc_mix_loss(output, img_l, patch_l, mask, l_weight=1.0, u_weight=0.5, unlab=False):
     """ACDC_BCP_train.py:167-179 -> (loss_dice, loss_ce)"""
     image_weight, patch_weight = l_weight, u_weight
@@ -415,7 +480,7 @@ def acdc_mix_loss(output, img_l, patch_l, mask, l_weight=1.0, u_weight=0.5, unla
     cl = BU._as_cl(output)
     ops = _ops_for(cl)
     N, sp = cl.shape[0], tuple(output.shape[2:])
-    box6, m8 = BU._mask_args(mask, ops, N, sp)
+    box6, m8 = BU._mask_args(mask, ops, N, sp, cl.device)
     return BU._MixLossFn.apply(cl, BU._labels_u8(ops, img_l, N, sp), BU._labels_u8(ops, patch_l, N, sp), box6, m8, H.LOSS_ACDC,
                                float(image_weight), float(patch_weight))
 
@@ -433,20 +498,22 @@ def update_model_ema(model, ema_model, alpha):
 
 
 def acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box=None, drops=None,
-                         u_weight=0.5, alpha=0.99, dp=None, grouped=True, overlap=True, plabs=None):
+                         u_weight=0.5, alpha=0.99, dp=None, grouped=True, overlap=True, plabs=None, mask_strategy=None):
+    _check_strategy(mask_strategy, ("random", "contact"))
     if not grouped and (getattr(model, "volatile_io", False) or getattr(ema_model, "volatile_io", False)):
         with _NoVolatileIO(model, ema_model):
             return acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box, drops, u_weight, alpha, dp, grouped,
-                                        overlap, plabs)
+                                        overlap, plabs, mask_strategy)
     return _acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box, drops, u_weight, alpha, dp, grouped, overlap,
-                                 plabs)
+                                 plabs, mask_strategy)
 
 
 def _acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch, labeled_bs, box=None, drops=None,
-                          u_weight=0.5, alpha=0.99, dp=None, grouped=True, overlap=True, plabs=None):
+                          u_weight=0.5, alpha=0.99, dp=None, grouped=True, overlap=True, plabs=None, mask_strategy=None):
     """One ACDC self-training iteration, ACDC_BCP_train.py:355-390 (grouped: see la_self_train_step; needs
     labeled_bs == batch - labeled_bs so that both halves have equal size).  plabs / optimizer=None: the parity hooks of
-    la_self_train_step (forced pseudo-labels; gradient-only mode)."""
+    la_self_train_step (forced pseudo-labels; gradient-only mode).  box: (w,h,pw,ph) or a list of such boxes; mask_strategy "random" /
+    "contact": the region is drawn by random_mask / contact_mask (ACDC_BCP_train.py:142-164) instead of generate_mask."""
     bs = volume_batch.shape[0]
     lsub, usub = int(labeled_bs / 2), int((bs - labeled_bs) / 2)
     grouped = grouped and lsub == usub
@@ -483,11 +550,14 @@ def _acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch
             pre_b = ema_model(uimg_b)
             plab_a = get_ACDC_masks(pre_a, nms=1)
             plab_b = get_ACDC_masks(pre_b, nms=1)
-        if box is None:
-            img_mask, loss_mask = generate_mask(img_a)
+        if box is not None:
+            img_mask, loss_mask = _explicit_masks(box, tuple(volume_batch.shape[2:]), lsub, volume_batch.device)
+        elif mask_strategy is not None:
+            img_mask, loss_mask = _draw_2d(mask_strategy, img_a)
         else:
-            sp = tuple(volume_batch.shape[2:])
-            img_mask, loss_mask = BU.BoxMask(box, sp, None, False, volume_batch.device), BU.BoxMask(box, sp, lsub, False, volume_batch.device)
+            img_mask, loss_mask = generate_mask(img_a)
+        if grouped:
+            _rasterise_early(loss_mask, volume_batch, lsub)
     own_plabs = (plab_a, plab_b)
     if plabs is not None:
         plab_a, plab_b = plabs[0].to(volume_batch.device), plabs[1].to(volume_batch.device)
@@ -553,17 +623,19 @@ def _acdc_self_train_step(model, ema_model, optimizer, volume_batch, label_batch
                 out_unl=out_unl.detach(), out_l=out_l.detach())
 
 
-def acdc_pre_train_step(model, optimizer, volume_batch, label_batch, box=None):
+def acdc_pre_train_step(model, optimizer, volume_batch, label_batch, box=None, mask_strategy=None):
     """One ACDC pre-training iteration, ACDC_BCP_train.py:236-256: image a with a box of image b pasted in, trained against both
-    label maps through mix_loss(u_weight=1.0, unlab=True); loss = (dice + ce) / 2"""
+    label maps through mix_loss(u_weight=1.0, unlab=True); loss = (dice + ce) / 2.  box / mask_strategy: as acdc_self_train_step"""
+    _check_strategy(mask_strategy, ("random", "contact"))
     sub_bs = volume_batch.shape[0] // 2
     img_a, img_b = volume_batch[:sub_bs], volume_batch[sub_bs:2 * sub_bs]
     lab_a, lab_b = label_batch[:sub_bs], label_batch[sub_bs:2 * sub_bs]
-    if box is None:
-        img_mask, loss_mask = generate_mask(img_a)
+    if box is not None:
+        img_mask, loss_mask = _explicit_masks(box, tuple(volume_batch.shape[2:]), sub_bs, volume_batch.device)
+    elif mask_strategy is not None:
+        img_mask, loss_mask = _draw_2d(mask_strategy, img_a)
     else:
-        sp = tuple(volume_batch.shape[2:])
-        img_mask, loss_mask = BU.BoxMask(box, sp, None, False, volume_batch.device), BU.BoxMask(box, sp, sub_bs, False, volume_batch.device)
+        img_mask, loss_mask = generate_mask(img_a)
     net_input = img_a * img_mask + img_b * (1 - img_mask)
     out = model(net_input)
     loss_dice, loss_ce = acdc_mix_loss(out, lab_a, lab_b, loss_mask, u_weight=1.0, unlab=True)

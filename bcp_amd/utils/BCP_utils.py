@@ -6,6 +6,8 @@ results, running on the gfx950 kernels.
   but returns `BoxMask` objects instead of two dense int64 tensors: they behave like the reference's
   masks in every expression the train scripts use (`a * m + b * (1 - m)`, passing to `mix_loss`,
   `.long()`, `.sum()`), while the kernels only ever see six integers.
+* `random_mask` (:30-46) and `concate_mask` (:48-56), the other masking strategies, return `RegionMask` objects (a union of boxes)
+  in the same way, with the reference's draws.
 * `mix_loss` (:58-69) is ONE fused forward pass + ONE backward pass over the logits (csrc/loss.hip).
 * `update_ema_variables` (:78-81) is one launch over the flat parameter buffer (bit-exact arithmetic).
 """
@@ -85,6 +87,137 @@ class BoxMask:
         return m
 
 
+class RegionMask:
+    """BoxMask's sibling for a UNION of boxes: the reference's random_mask (27 boxes, :30-46; ACDC_BCP_train.py:142-154, 9 boxes) and
+    concate_mask / contact_mask (one slab, :48-56; ACDC_BCP_train.py:156-164).  Same tensor-like surface.  What the kernels see depends on
+    the box count: exactly one box goes to the box kernels (bcp_mix_box, the loss's arithmetic box test: bit-identical to a BoxMask, nothing
+    rasterised); any other count is rasterised ONCE per draw into a uint8 map (bcp_mask_boxes) that the image mix (bcp_mix_mask) and the
+    loss (mask_or_null) both read -- the image mask, the loss mask and their complements of one draw share `_shared`, the map cache."""
+
+    def __init__(self, boxes, spatial, batch=None, complement=False, device=None, _shared=None):
+        self.spatial = tuple(int(v) for v in spatial)
+        nd = len(self.spatial)
+        self.boxes = tuple(tuple(int(v) for v in b) for b in boxes)      # 3-D: (w, h, z, pw, ph, pz); 2-D: (w, h, pw, ph)
+        if any(len(b) != 2 * nd for b in self.boxes):
+            raise ValueError(f"RegionMask: every box of a {nd}-D region is {2 * nd} integers")
+        if any(v < 0 for b in self.boxes for v in b[nd:]):
+            raise ValueError("RegionMask: negative box size")
+        self.batch = batch
+        self.complement = complement
+        self.device = device
+        self._shared = _shared if _shared is not None else {"n": batch or 1, "maps": {}, "count": None}
+        if batch is not None:
+            self._shared["n"] = max(self._shared["n"], int(batch))
+
+    def _like(self, batch, complement):
+        return RegionMask(self.boxes, self.spatial, batch, complement, self.device, self._shared)
+
+    def with_batch(self, batch):
+        """the [N, ...] loss mask of this draw (shares the rasterised map)"""
+        return self._like(batch, self.complement)
+
+    # ---- tensor-like surface used by the train scripts
+    @property
+    def shape(self):
+        return torch.Size(((self.batch,) if self.batch is not None else ()) + self.spatial)
+
+    def boxes6(self):
+        if len(self.spatial) == 3:
+            return self.boxes
+        return tuple((0, w, h, 1, pw, ph) for w, h, pw, ph in self.boxes)
+
+    def single(self):
+        """the region is exactly one box: the box kernels serve it"""
+        return len(self.boxes) == 1
+
+    def long(self):
+        return self
+
+    def unsqueeze(self, _dim):
+        return self
+
+    def type(self, *_a, **_k):
+        return self
+
+    def __rsub__(self, other):
+        if other == 1:
+            return self._like(self.batch, not self.complement)
+        return NotImplemented
+
+    def __mul__(self, t):
+        return _Masked(t, self)
+
+    __rmul__ = __mul__
+
+    def _union(self):
+        """voxels of the union (boxes clamped to the volume, overlaps counted once): coordinate compression, no dense map"""
+        if self._shared["count"] is None:
+            nd = len(self.spatial)
+            lim = [[(min(max(b[ax], 0), self.spatial[ax]), min(max(b[ax] + b[nd + ax], 0), self.spatial[ax])) for ax in range(nd)] for b in self.boxes]
+            edges = [np.unique([0, self.spatial[ax]] + [v for l in lim for v in l[ax]]) for ax in range(nd)]
+            cells = np.zeros([len(e) - 1 for e in edges], dtype=bool)
+            for l in lim:
+                if all(lo < hi for lo, hi in l):
+                    cells[tuple(slice(int(np.searchsorted(edges[ax], l[ax][0])), int(np.searchsorted(edges[ax], l[ax][1]))) for ax in range(nd))] = True
+            size = np.ones((), dtype=np.int64)
+            for ax in range(nd):
+                size = size[..., None] * np.diff(edges[ax]).astype(np.int64)
+            self._shared["count"] = int((size * cells).sum())
+        return self._shared["count"]
+
+    def count(self):
+        vol = int(np.prod(self.spatial))
+        n = (vol - self._union()) if not self.complement else self._union()
+        return n * (self.batch if self.batch is not None else 1)
+
+    def sum(self):
+        return torch.tensor(self.count(), dtype=torch.int64)
+
+    def tensor(self, device=None, dtype=torch.int64):
+        """materialise the dense mask (compatibility / visualisation only)"""
+        m = torch.ones(self.spatial, dtype=dtype, device=device or self.device)
+        nd = len(self.spatial)
+        for b in self.boxes:
+            m[tuple(slice(max(b[ax], 0), max(b[ax] + b[nd + ax], 0)) for ax in range(nd))] = 0
+        if self.complement:
+            m = 1 - m
+        if self.batch is not None:
+            m = m.unsqueeze(0).repeat(self.batch, *([1] * nd))
+        return m
+
+    def u8(self, ops, N=None, device=None):
+        """the device map uint8 [N, D, H, W] (2-D: D = 1) of this mask, 1 = image term: ONE bcp_mask_boxes launch per draw -- the first call
+        rasterises for the largest batch the draw's masks were made for, later calls (the loss mask after the image mask, any smaller N)
+        get views of the same buffer.  device: where the map is needed (the tensors it is used with); default: the mask's own."""
+        n = int(N) if N is not None else (self.batch or 1)
+        device = torch.device(device if device is not None else (self.device if self.device is not None else "cpu"))
+        if device.type == "cuda" and device.index is None:      # "cuda" and "cuda:0" are one device: one map, one launch
+            device = torch.device("cuda", torch.cuda.current_device())
+        maps, key = self._shared["maps"], (self.complement, device)
+        have = maps.get(key)
+        if have is None or have.shape[0] < n:
+            sp = self.spatial if len(self.spatial) == 3 else (1,) + self.spatial
+            have = maps[key] = ops.mask_boxes(self.boxes6(), (max(n, self._shared["n"]),) + sp, device, self.complement)
+        return have[:n]
+
+    def _dense(self, device, dtype):
+        """tensor() of the un-complemented [spatial] mask, kept per (device, dtype) for the draw: what the dense torch fallback of mix()
+        multiplies with (read-only there) -- materialising it is one slice fill per box"""
+        d = self._shared.setdefault("dense", {})
+        key = (torch.device(device), dtype)
+        if key not in d:
+            d[key] = self._like(None, False).tensor(device, dtype)
+        return d[key]
+
+
+def _same_region(m1, m2):
+    if isinstance(m1, BoxMask) and isinstance(m2, BoxMask):
+        return m1.box == m2.box
+    if isinstance(m1, RegionMask) and isinstance(m2, RegionMask):
+        return m1.boxes == m2.boxes and m1.spatial == m2.spatial
+    return False
+
+
 class _Masked:
     """`t * mask`; adding the complementary term launches the fused copy-paste kernel"""
 
@@ -92,7 +225,7 @@ class _Masked:
         self.t, self.mask = t, mask
 
     def __add__(self, other):
-        if not isinstance(other, _Masked) or other.mask.box != self.mask.box or other.mask.complement == self.mask.complement:
+        if not isinstance(other, _Masked) or not _same_region(other.mask, self.mask) or other.mask.complement == self.mask.complement:
             return self.dense() + (other.dense() if isinstance(other, _Masked) else other)
         outside, inside = (self, other) if not self.mask.complement else (other, self)
         return mix(outside.t, inside.t, self.mask)
@@ -106,17 +239,24 @@ class _Masked:
         return self.dense().sum(*a, **k)
 
 
-def mix(a, b, mask: BoxMask, out=None):
-    """a*mask + b*(1-mask) (LA_BCP_train.py:248-251): `a` outside the box, `b` inside."""
+def mix(a, b, mask, out=None):
+    """a*mask + b*(1-mask) (LA_BCP_train.py:248-251): `a` outside the box (or the union of boxes of a RegionMask), `b` inside."""
     if a.dtype != torch.float32 or a.dim() not in (4, 5) or a.shape[1] != 1:
-        m = mask.tensor(a.device, a.dtype) if not mask.complement else (1 - mask).tensor(a.device, a.dtype)
+        if isinstance(mask, RegionMask):
+            m = mask._dense(a.device, a.dtype)
+        else:
+            m = mask.tensor(a.device, a.dtype) if not mask.complement else (1 - mask).tensor(a.device, a.dtype)
         return a * m + b * (1 - m)
     ops = Ops.product() if a.is_cuda else _cpu_ops()
     N = a.shape[0]
     sp = tuple(a.shape[2:])
     cl_shape = (N,) + ((1,) + sp if len(sp) == 2 else sp) + (1,)
-    o = ops.mix_box(a.contiguous().view(cl_shape), b.contiguous().view(cl_shape), mask.box6(),
-                    out=None if out is None else out.view(cl_shape))
+    ac, bc, oc = a.contiguous().view(cl_shape), b.contiguous().view(cl_shape), None if out is None else out.view(cl_shape)
+    if isinstance(mask, RegionMask) and not mask.single():
+        m8 = (mask if not mask.complement else 1 - mask).u8(ops, device=a.device)[0]      # one [D,H,W] map for every sample
+        o = ops.mix_mask(ac, bc, m8, out=oc)
+    else:
+        o = ops.mix_box(ac, bc, mask.boxes6()[0] if isinstance(mask, RegionMask) else mask.box6(), out=oc)
     return o.view(a.shape)
 
 
@@ -150,6 +290,38 @@ def context_mask(img, mask_ratio):
     box = (w, h, z, patch_pixel_x, patch_pixel_y, patch_pixel_z)
     sp = (img_x, img_y, img_z)
     return BoxMask(box, sp, None, False, img.device), BoxMask(box, sp, batch_size, False, img.device)
+
+
+def _region_pair(boxes, spatial, batch_size, device):
+    """(img_mask, loss_mask) of one draw: two views of one region, sharing its rasterised map"""
+    loss_mask = RegionMask(boxes, spatial, batch_size, False, device)
+    return loss_mask._like(None, False), loss_mask
+
+
+def random_mask(img):
+    """reference :30-46: 27 zero boxes, one per cell of a 3x3x3 grid; 81 np.random.randint draws (cells in xs, ys, zs order; w, h, z per
+    cell).  Patches too small for the grid make randint raise, as in the reference."""
+    batch_size, channel, img_x, img_y, img_z = img.shape[0], img.shape[1], img.shape[2], img.shape[3], img.shape[4]
+    patch_pixel_x, patch_pixel_y, patch_pixel_z = int(img_x * 2 / 3), int(img_y * 2 / 3), int(img_z * 2 / 3)
+    mask_size_x, mask_size_y, mask_size_z = int(patch_pixel_x / 3) + 1, int(patch_pixel_y / 3) + 1, int(patch_pixel_z / 3)
+    size_x, size_y, size_z = int(img_x / 3), int(img_y / 3), int(img_z / 3)
+    boxes = []
+    for xs in range(3):
+        for ys in range(3):
+            for zs in range(3):
+                w = np.random.randint(xs * size_x, (xs + 1) * size_x - mask_size_x - 1)
+                h = np.random.randint(ys * size_y, (ys + 1) * size_y - mask_size_y - 1)
+                z = np.random.randint(zs * size_z, (zs + 1) * size_z - mask_size_z - 1)
+                boxes.append((w, h, z, mask_size_x, mask_size_y, mask_size_z))
+    return _region_pair(boxes, (img_x, img_y, img_z), batch_size, img.device)
+
+
+def concate_mask(img):
+    """reference :48-56: one full-width zero slab along z, int(img_z * 8 / 27) thick; one np.random.randint draw"""
+    batch_size, channel, img_x, img_y, img_z = img.shape[0], img.shape[1], img.shape[2], img.shape[3], img.shape[4]
+    z_length = int(img_z * 8 / 27)
+    z = np.random.randint(0, img_z - z_length - 1)
+    return _region_pair([(0, 0, z, img_x, img_y, z_length)], (img_x, img_y, img_z), batch_size, img.device)
 
 
 def _as_cl(out):
@@ -312,7 +484,7 @@ def mix_loss_pair(out, first, second, mask, flavour=H.LOSS_LA, total=False):
     cl = _as_cl(out)
     ops = _ops_for(cl)
     N, sp = cl.shape[0] // 2, tuple(out.shape[2:])
-    box6, m8 = _mask_args(mask, ops, N, sp)
+    box6, m8 = _mask_args(mask, ops, N, sp, cl.device)
     l1, p1, w1a, w1b = first
     l2, p2, w2a, w2b = second
     fn = _MixLossPairTotalFn if total else _MixLossPairFn
@@ -333,12 +505,18 @@ def unit_gradient(like):
     return o
 
 
-def _mask_args(mask, ops, N, sp):
-    """-> (box6, dense uint8 mask or None)"""
+def _mask_args(mask, ops, N, sp, device=None):
+    """-> (box6, dense uint8 mask or None); device: the logits' (where a RegionMask's map has to live)"""
     if isinstance(mask, BoxMask):
         if mask.complement:
             raise ValueError("pass the loss mask itself, not its complement")
         return mask.box6(), None
+    if isinstance(mask, RegionMask):
+        if mask.complement:
+            raise ValueError("pass the loss mask itself, not its complement")
+        if mask.single():
+            return mask.boxes6()[0], None
+        return (0, 0, 0, 0, 0, 0), mask.u8(ops, N, device)      # the draw's one rasterised map: no cast launch between forward and backward
     m = ops.to_u8(mask if mask.dim() == len(sp) + 1 else mask.expand((N,) + sp))
     return (0, 0, 0, 0, 0, 0), m.view((N,) + ((1,) + sp if len(sp) == 2 else sp))
 
@@ -351,7 +529,7 @@ def mix_loss(net3_output, img_l, patch_l, mask, l_weight=1.0, u_weight=0.5, unla
     cl = _as_cl(net3_output)
     ops = _ops_for(cl)
     N, sp = cl.shape[0], tuple(net3_output.shape[2:])
-    box6, m8 = _mask_args(mask, ops, N, sp)
+    box6, m8 = _mask_args(mask, ops, N, sp, cl.device)
     return _MixLossFn.apply(cl, _labels_u8(ops, img_l, N, sp), _labels_u8(ops, patch_l, N, sp), box6, m8, H.LOSS_LA,
                             float(image_weight), float(patch_weight))
 

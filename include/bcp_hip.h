@@ -42,7 +42,7 @@ enum { BCP_WG_DOWN = 0, BCP_WG_UP = 1, BCP_WG_PW = 2 };
 /* ABI revision = 100 * round + change counter.  Bumped whenever an exported signature changes; a binding must refuse a library whose
  * bcp_version() differs from the header it was written against (bcp_amd/_lib.py does: a stale in-tree .so then fails at load, not
  * with shifted arguments inside a launch). */
-#define BCP_ABI_VERSION 511
+#define BCP_ABI_VERSION 512
 int bcp_version(void);
 const char* bcp_last_error(void);
 /* process-wide tuning / test switches (the library never reads the environment): name = a field of bcp::Options
@@ -68,6 +68,21 @@ int bcp_event_destroy(void* ev);
  *      16-byte vector path only: W * C must be a multiple of 4 (80, 96 and 256 in the reference's configurations); other extents are
  *      rejected with BCP_EINVAL. */
 int bcp_mix_box(const float* a, const float* b, float* out, int N, int D, int H, int W, int C, const int* box6 /* HOST */, void* stream);
+
+/* ---- copy-paste regions that are a UNION of boxes: the paper's other masking strategies -- 27 small boxes, one per cell of a 3x3x3 grid
+ *      (utils/BCP_utils.py:30-46 random_mask), one full-width slab along z (utils/BCP_utils.py:48-56 concate_mask), 9 boxes on a 3x3
+ *      grid (ACDC_BCP_train.py:142-154 random_mask), one full-width band (ACDC_BCP_train.py:156-164 contact_mask).
+ *      bcp_mask_boxes writes the uint8 map [N][D][H][W], every sample the same: 0 inside the union of the K boxes (each as box6 of
+ *      bcp_mix_box: d, h, w, size_d, size_h, size_w), 1 elsewhere; complement != 0 swaps the two values.  Boxes may overlap and may
+ *      reach past the volume (they are clamped); a negative size, K > 32 (the boxes travel as kernel arguments) or W % 4 != 0 is
+ *      BCP_EINVAL; K == 0 writes all ones.  The map is what the loss entries below take as mask_or_null (1 = image term).
+ *      bcp_mix_mask: out = mask ? a : b per voxel of single-channel images [N][D][H][W] -- a SELECT, not a*m + b*(1-m): every value
+ *      passes through bit for bit, NaN and -0.0 included (bcp_mix_box selects in the same way).  mask_sample_stride (bytes = voxels):
+ *      0 = one [D][H][W] map shared by all samples, else the distance between the samples' maps (a multiple of 4).  Pointer alignment
+ *      and size limits as bcp_mix_box (16 B for a / b / out, W % 4 == 0, < 2^31 floats); the mask is read as 32-bit words (4-B aligned). */
+int bcp_mask_boxes(uint8_t* out, int N, int D, int H, int W, const int* boxes /* HOST, K x 6 */, int K, int complement, void* stream);
+int bcp_mix_mask(const float* a, const float* b, const uint8_t* mask, float* out, int N, int D, int H, int W, long long mask_sample_stride,
+                 void* stream);
 
 /* ---- pseudo-labels (LA_BCP_train.py:57-60 get_cut_mask; ACDC_BCP_train.py:112-114 get_ACDC_masks) ---------- */
 int bcp_plabel_bin(const float* logits /*[n_vox][2]*/, uint8_t* out, long long n_vox, float thres, void* stream);
