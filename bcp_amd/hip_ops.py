@@ -1110,6 +1110,7 @@ def _profiled(name, fn):
         return r
     wrapper.__name__ = name
     wrapper.__doc__ = fn.__doc__
+    wrapper.__wrapped__ = fn          # (inspect.signature of a profiled op is the op's own)
     return wrapper
 
 

@@ -2,13 +2,17 @@
 
 STEP_KEYS holds what `Ops.profile_end()` records for each call of a replayed step: (op, shapes of the first three tensor arguments, first
 three int arguments, number of the first two tensors that carry `_bcp_amax`).  The key carries no keyword arguments, so STEP_VARIANTS adds,
-per norm key, the epilogues the step's norm calls really use (fused partials, channel scale, dropout, residual, statistics only, slab
-output), read off a step by `record_step_variants`.  tests/test_gpu_product_ops.py asserts that a real step records nothing outside the
-two tables and runs DRIVERS over the rows whose op family has one (`driven_rows()`).
+per key, the flags the step's calls really pass (norm epilogues: fused partials, channel scale, dropout, residual, statistics only, slab
+output; elsewhere: accumulate, an output buffer given, an upstream gradient on the device), read off a step by `record_step_variants`.
+tests/test_gpu_product_ops.py asserts that a real step records nothing outside the two tables and runs DRIVERS over every row
+(`driven_rows()`); tests/test_product_ops_cpu.py asserts that every op of the table has a driver.
 
-This covers part of the steps' ops only.  Families without a driver, still checked only by tests/kernel_checks.py at small shapes and by
-the whole-step comparisons: the fused first-layer convs (conv3_c1_*), the k2s2 / transposed / pointwise convs (down_*, up_*, k2_*,
-pw_*, pw16_*), norm_*_slabs, the losses (mixloss_pair_*, ACDC dice_prob), mix_box and the weight packs.
+Every op family of the three steps has one: the 3x3(x3) convs and their weight gradients, the norms (plain and on split-K slabs), the
+fused first layer (conv3_c1_*), the k2s2 / transposed / pointwise convs on the GEMM route (down_*, up_*, k2_*, pw_fwd), the fused 16 -> C
+head (pw16_*), the pools and the bilinear x2, the paired mix loss and its gradient against a closed form pinned to the oracle's
+autograd, mix_box and the largest-component filter bit for bit, the networks' batched weight packs bit for bit against the single-layer
+packs, the optimisers.  Rows stay at the in-step shapes because the route is a function of the shape (csrc/gemm.hip: pick_nt, stat_plan,
+tn_groups; split-K slab counts; fused statistics): each driver asserts on the device that the in-step route was taken.
 
 The comparator: every element is held to |out - ref64| <= tau * cond, where cond is the same linear op applied in fp64 to |x| and |w| (a
 per-element bound on what rounding can do).  A rel-L2 test spreads an error confined to one tile over the whole tensor; this one does not.
@@ -120,6 +124,51 @@ def conv3_wgrad64(x, dy, k=3, two_d=False):
             for c in range(k):
                 g[:, :, a, b, c] = dyf.t() @ xp[:, a:a + D, b:b + H, c:c + W, :].reshape(-1, Ci)
     return g[:, :, 0] if two_d else g
+
+
+_SUBS = [(a, b, c) for a in range(2) for b in range(2) for c in range(2)]       # the (a, b, c) sub-positions of a 2x2x2 stride-2 kernel
+
+
+def down64(x, w):
+    """k2s2 conv of a channels-last [N, D, H, W, Cin] tensor (even extents) with w [Cout, Cin, 2, 2, 2], in fp64:
+    y[n, d, h, w, :] = sum over (a, b, c) of x[n, 2d+a, 2h+b, 2w+c, :] @ W[:, :, a, b, c].T -- eight strided-view matmuls.
+    With w a ConvTranspose3d weight [Cin_t, Cout_t, 2, 2, 2] and x = dy this is that layer's dgrad."""
+    x, w = x.double().cpu(), w.double().cpu()
+    N, D, H, W, Ci = x.shape
+    assert D % 2 == 0 and H % 2 == 0 and W % 2 == 0 and w.shape[1] == Ci, (x.shape, w.shape)
+    y = torch.zeros(N, D // 2, H // 2, W // 2, w.shape[0], dtype=torch.float64)
+    for a, b, c in _SUBS:
+        y += x[:, a::2, b::2, c::2] @ w[:, :, a, b, c].t()
+    return y
+
+
+def up64(x, w):
+    """transposed k2s2 conv of a channels-last [N, D, H, W, Cin] tensor with w [Cin, Cout, 2, 2, 2], in fp64:
+    y[n, 2d+a, 2h+b, 2w+c, :] = x[n, d, h, w, :] @ W[:, :, a, b, c].  With w a Conv3d weight [Cout_c, Cin_c, 2, 2, 2] and x = dy this is
+    that layer's dgrad."""
+    x, w = x.double().cpu(), w.double().cpu()
+    N, D, H, W, Ci = x.shape
+    assert w.shape[0] == Ci, (x.shape, w.shape)
+    y = torch.zeros(N, 2 * D, 2 * H, 2 * W, w.shape[1], dtype=torch.float64)
+    for a, b, c in _SUBS:
+        y[:, a::2, b::2, c::2] = x @ w[:, :, a, b, c]
+    return y
+
+
+def k2_wgrad64(x, dy, kind):
+    """weight gradient of the down conv (kind 0: x fine, dy coarse -> [Cout, Cin, 2, 2, 2]), the transposed conv (1: x coarse, dy fine ->
+    [Cin, Cout, 2, 2, 2]) and the 1x1 conv (2: one grid -> [Cout, Cin, 1, 1]): per sub-position dy^T @ x (resp. x^T @ dy), in fp64"""
+    x, dy = x.double().cpu(), dy.double().cpu()
+    Cx, Cy = x.shape[-1], dy.shape[-1]
+    if kind == 2:
+        return (dy.reshape(-1, Cy).t() @ x.reshape(-1, Cx)).reshape(Cy, Cx, 1, 1)
+    g = torch.zeros(((Cy, Cx) if kind == 0 else (Cx, Cy)) + (2, 2, 2), dtype=torch.float64)
+    for a, b, c in _SUBS:
+        if kind == 0:
+            g[:, :, a, b, c] = dy.reshape(-1, Cy).t() @ x[:, a::2, b::2, c::2].reshape(-1, Cx)
+        else:
+            g[:, :, a, b, c] = x.reshape(-1, Cx).t() @ dy[:, a::2, b::2, c::2].reshape(-1, Cy)
+    return g
 
 
 # -------------------------------------------------------------------------------------------------- the steps' keys
@@ -620,6 +669,17 @@ def _stats_check(st, mu, var, tag):
     assert em <= TAU and er <= TAU, f"{tag}: statistics off (mean {em:.3e}, rstd {er:.3e})"
 
 
+def _running_check(tag, rm, rv, rm0, rv0, mu, var, n):
+    """BatchNorm's running statistics after one grouped call (momentum 0.1, one update per group, unbiased variance over n voxels)"""
+    m64, v64 = rm0.double(), rv0.double()
+    for gi in range(mu.shape[0]):
+        m64 = 0.9 * m64 + 0.1 * mu[gi, 0]
+        v64 = 0.9 * v64 + 0.1 * var[gi, 0] * n / (n - 1)
+    for t, r in ((rm, m64), (rv, v64)):
+        e = float(((t.double().cpu() - r).abs() / (r.abs() + mu.abs().amax((0, 1)) + 1e-30)).max())
+        assert e <= TAU, f"{tag}: running statistics off by {e:.3e}"
+
+
 def drive_norm_fwd(ops, dev, key, g, variants=((),)):
     """norm_fwd with each epilogue the step uses at this key (STEP_VARIANTS): statistics from a real conv3_fwd_stats launch's fused
     partials, channel scale, seeded elementwise dropout, residual, statistics only, a concat-buffer slab as output; ReLU (V-Net) /
@@ -666,14 +726,7 @@ def drive_norm_fwd(ops, dev, key, g, variants=((),)):
         else:
             out.append((op + " " + "+".join(flags), (0.0, "stats")))
         if rm is not None:
-            n = y.numel() // C // G
-            m64, v64 = rm0.double(), rv0.double()
-            for gi in range(G):
-                m64 = 0.9 * m64 + 0.1 * mu[gi, 0]
-                v64 = 0.9 * v64 + 0.1 * var[gi, 0] * n / (n - 1)
-            for t, r in ((rm, m64), (rv, v64)):
-                e = float(((t.double().cpu() - r).abs() / (r.abs() + mu.abs().amax((0, 1)) + 1e-30)).max())
-                assert e <= TAU, f"{tag}: running statistics off by {e:.3e}"
+            _running_check(tag, rm, rv, rm0, rv0, mu, var, y.numel() // C // G)
     return out
 
 
@@ -682,6 +735,42 @@ def _kink(z, fcond):
     statistics (a few ulps of fcond off the fp64 value), so there it may take the other branch -- a whole |da| of difference, not a
     rounding error (one such element, z = 3.9e-8 at fcond 1.35, moved dbeta by 9e-5 of sum |dz| at 2 x 14 x 14 x 10 x 128)"""
     return z.abs() <= 2.0 ** -18 * fcond
+
+
+def _norm_bwd_ref64(y, G, gam, bet, act, da64, mult, zcond=None):
+    """fp64 backward of norm_ref64 for the incoming gradient da64 * mult -> (dy ref, its cond, dz, xhat, dk), the last three as
+    [G, n, C]; dk: the terms of elements at the activation's kink (_kink), which may take either branch.  zcond: what else the kernel's
+    pre-activation can move by per unit of rounding (a y it recomputes in fp32), added to the norm's own cond in the kink test"""
+    ys = tuple(y.shape)
+    C = ys[-1]
+    _, z, xh, _, var, fcond = norm_ref64(y, G, gam, bet, act)
+    kink = _kink(z, fcond if zcond is None else fcond + zcond)
+    _, dact = _acts(act, z)
+    dz = (da64 * mult * dact).reshape(G, -1, C)
+    xg = xh.reshape(G, -1, C)
+    dk = (da64 * mult * kink).abs().reshape(G, -1, C)      # (a kink element may take either branch: its whole term is allowed)
+    rstd = 1.0 / torch.sqrt(var + EPS)
+    gm = torch.ones(C, dtype=torch.float64) if gam is None else gam.double()
+    m1, m2 = dz.mean(1, keepdim=True), (dz * xg).mean(1, keepdim=True)
+    ref = (gm * rstd * (dz - m1 - xg * m2)).reshape(ys)
+    # the two means are fp32-staged reductions over n = voxels per group; their rounding grows with the reduction depth, ~log2(n).
+    # Without the factor the pancreas InstanceNorm at 2 x 48^3 x 32 (n = 110 592) measured 2.1 x TAU, with it 0.32 x TAU at worst.
+    kap = float(np.log2(dz.shape[1]))
+    cond = (gm * rstd * (dz.abs() + kap * (dz.abs().mean(1, keepdim=True) + xg.abs() * (dz * xg).abs().mean(1, keepdim=True)))).reshape(ys)
+    cond = torch.where(kink, torch.full_like(cond, float("inf")), cond)
+    return ref, cond, dz, xg, dk
+
+
+def _dgamma_dbeta_check(tag, dg, db, dg0, db0, dz, xg, dk, dzb=None):
+    """the accumulated dgamma / dbeta against their fp64 sums (plus what they held), less the kink allowance; dzb: a bound on |dz| where
+    dz is itself a rounded sum (the slab kernels), else |dz|"""
+    sdb, sdg = dz.sum((0, 1)), (dz * xg).sum((0, 1))
+    dzb = dz.abs() if dzb is None else dzb
+    for name, t, base, s_, c, k in (("dbeta", db, db0, sdb, dzb.sum((0, 1)), dk.sum((0, 1))),
+                                    ("dgamma", dg, dg0, sdg, (dzb * xg.abs()).sum((0, 1)), (dk * xg.abs()).sum((0, 1)))):
+        err = ((t.double().cpu() - (base.double() + s_)).abs() - k).clamp_min(0)
+        r, _ = elementwise_ratio(err, torch.zeros_like(err), base.double().abs() + c)
+        assert r <= TAU, f"{tag}: {name} off by {r:.3e} x cond"
 
 
 def drive_norm_bwd(ops, dev, key, g, variants=((),)):
@@ -703,9 +792,6 @@ def drive_norm_bwd(ops, dev, key, g, variants=((),)):
         yd = y.to(dev)
         _, st = ops.norm_fwd(yd, G, *((gam.to(dev), bet.to(dev), torch.zeros(C, device=dev), torch.ones(C, device=dev)) if affine else (None,) * 4), act)
         cs, sm, es, _, mult, H = _epilogue(ops, dev, g, ys, flags)
-        _, z, xh, _, var, fcond = norm_ref64(y, G, gam, bet, act)
-        kink = _kink(z, fcond)
-        _, dact = _acts(act, z)
         part, rows = None, 0
         if "partial" in flags:
             dad, part, rows = _conv_partial_source(ops, dev, g, ys, G, fwd=False, yprev=yd, stats=st, act=act)
@@ -714,9 +800,7 @@ def drive_norm_bwd(ops, dev, key, g, variants=((),)):
         else:
             da = gradient(g, ys)
             dad = da.to(dev)
-        dz = (da.double() * mult * dact).reshape(G, -1, C)
-        xg = xh.reshape(G, -1, C)
-        dk = (da.double() * mult * kink).abs().reshape(G, -1, C)      # (a kink element may take either branch: its whole term is allowed)
+        ref, cond, dz, xg, dk = _norm_bwd_ref64(y, G, gam, bet, act, da.double(), mult)
         if rows:
             ps = _partials(part, G, rows, C)
             for j, (s, c, k) in enumerate(((dz.sum(1), dz.abs().sum(1), dk.sum(1)),
@@ -730,23 +814,9 @@ def drive_norm_bwd(ops, dev, key, g, variants=((),)):
         if rows:
             kw.update(partial=part, nb=rows)
         dx = ops.norm_bwd(yd, dad, G, st, act, dg, db, accumulate, **kw)
-        rstd = 1.0 / torch.sqrt(var + EPS)
-        gm = torch.ones(C, dtype=torch.float64) if gam is None else gam.double()
-        m1, m2 = dz.mean(1, keepdim=True), (dz * xg).mean(1, keepdim=True)
-        ref = (gm * rstd * (dz - m1 - xg * m2)).reshape(ys)
-        # the two means are fp32-staged reductions over n = voxels per group; their rounding grows with the reduction depth, ~log2(n).
-        # Without the factor the pancreas InstanceNorm at 2 x 48^3 x 32 (n = 110 592) measured 2.1 x TAU, with it 0.32 x TAU at worst.
-        kap = float(np.log2(dz.shape[1]))
-        cond = (gm * rstd * (dz.abs() + kap * (dz.abs().mean(1, keepdim=True) + xg.abs() * (dz * xg).abs().mean(1, keepdim=True)))).reshape(ys)
-        cond = torch.where(kink, torch.full_like(cond, float("inf")), cond)
         out.append((op + ("" if not flags else " " + "+".join(flags)), check_elementwise(dx.cpu(), ref, cond, TAU, tag)))
         if affine:
-            sdb, sdg = dz.sum((0, 1)), (dz * xg).sum((0, 1))
-            for name, t, base, s_, c, k in (("dbeta", db, db0, sdb, dz.abs().sum((0, 1)), dk.sum((0, 1))),
-                                            ("dgamma", dg, dg0, sdg, (dz * xg).abs().sum((0, 1)), (dk * xg.abs()).sum((0, 1)))):
-                err = ((t.double().cpu() - (base.double() + s_)).abs() - k).clamp_min(0)
-                r, _ = elementwise_ratio(err, torch.zeros_like(err), base.double().abs() + c)
-                assert r <= TAU, f"{tag}: {name} off by {r:.3e} x cond"
+            _dgamma_dbeta_check(tag, dg, db, dg0, db0, dz, xg, dk)
     return out
 
 
@@ -938,11 +1008,567 @@ def drive_cc(ops, dev, key, g):
     return out
 
 
+def _k2_weight(g, shape, fan_in):
+    """a k2s2 / transposed / 1x1 conv weight drawn as _conv_weight draws the 3x3x3 ones, scaled for its fan-in"""
+    return (torch.randn(shape, generator=g, dtype=torch.float64) * (2.0 / fan_in) ** 0.5).float()
+
+
+# k2_fwd_stats: each partial row sums fp32 lane partials of the GEMM epilogue (<= 256 values each), the rows are summed in fp64: the
+# 1e-12 of conv3_fwd_stats (fp64 throughout) does not hold.  Measured on the device, worst |partial sum - fp64 sum| / sum |.| over
+# groups and channels: LA 2 x 56 x 56 x 40 x 32 -> 16 (980 rows) 2.81e-10 (sum) / 1.63e-9 (sum of squares), pancreas 2 x 48^3 x 32 -> 16
+# (864 rows) 3.75e-10 / 1.89e-9.  The bound is twice the worst.
+TAU_K2_STATS_MEASURED = 1.89e-9
+TAU_K2_STATS = 2 * TAU_K2_STATS_MEASURED
+
+
+def drive_k2(ops, dev, key, g, variants=((),)):
+    """down_fwd / down_dgrad / up_fwd / up_dgrad / k2_fwd_stats / k2_wgrad / pw_fwd at the step's row counts, against the strided-view
+    fp64 matmuls (down64, up64, k2_wgrad64).  The weights go through ops.k2_pack with the launch's PACK_* kind; the flags of `variants`
+    (out given, accumulate) are the step's: down_dgrad adds into the skip gradient, every k2_wgrad into the flat gradient buffer."""
+    from bcp_amd import hip_ops as H
+    op, shapes, ints, namax = key
+    xs = shapes[0]
+    two_d = xs[1] == 1
+    tile = (1, 16, 16) if two_d else (4, 8, 8)
+    out = []
+    for flags in variants:
+        tag = f"{op} {xs} {ints} [{'+'.join(flags) or 'plain'}]"
+        name = op + ("" if not flags else " " + "+".join(flags))
+        acc = "accumulate" in flags
+        if op == "k2_wgrad":
+            _, dys, ws = shapes
+            kind = ints[0]
+            x, dy = activation(g, xs), gradient(g, dys)
+            xd, dyd = x.to(dev), dy.to(dev)
+            for t in (xd, dyd)[:namax]:
+                _amax(H, t, dev)
+            ref = k2_wgrad64(x, dy, kind).reshape(ws)
+            cond = k2_wgrad64(x.abs(), dy.abs(), kind).reshape(ws)
+            dw0 = gradient(g, ws, -4.0, 0.0)
+            dwd = dw0.clone().to(dev) if acc else torch.full(ws, float("nan"), device=dev)
+            res = ops.k2_wgrad(xd, dyd, dwd, kind, accumulate=acc)
+            if acc:
+                ref, cond = ref + dw0.double(), cond + dw0.double().abs()
+            out.append((name, check_elementwise(res.cpu(), ref, cond, TAU, tag)))
+            continue
+        Cx = xs[-1]
+        Co = ints[1] if op == "k2_fwd_stats" else ints[0]          # channels of the result
+        kind = {"down_fwd": 0, "up_fwd": 1, "down_dgrad": 1, "up_dgrad": 0, "pw_fwd": 2}.get(op, ints[0])     # the reference: down64 / up64 / 1x1
+        fwd = op in ("down_fwd", "up_fwd", "k2_fwd_stats") or (op == "pw_fwd" and len(shapes) > 2)
+        x = activation(g, xs) if fwd else gradient(g, xs)
+        xd = x.to(dev)
+        if namax:
+            _amax(H, xd, dev)
+        b = (torch.randn(Co, generator=g) * 0.1) if fwd else None
+        bd = None if b is None else b.to(dev)
+        # the layer's own weight: Conv3d [Cout, Cin, 2, 2, 2] (down, 1x1) or ConvTranspose3d [Cin, Cout, 2, 2, 2] (up); a dgrad maps Cout -> Cin
+        Cin, Cout = (Cx, Co) if fwd else (Co, Cx)
+        if op in ("down_fwd", "down_dgrad") or (op == "k2_fwd_stats" and kind == 0):
+            w = _k2_weight(g, (Cout, Cin, 2, 2, 2), 8 * Cin)
+            pk = H.PACK_DOWN_FWD if fwd else H.PACK_DOWN_DGRAD
+        elif op == "pw_fwd":
+            w = _k2_weight(g, (Cout, Cin, 1, 1), Cin)
+            pk = H.PACK_PW_FWD if fwd else H.PACK_PW_DGRAD
+        else:
+            w = _k2_weight(g, (Cin, Cout, 2, 2, 2), 8 * Cin)
+            pk = H.PACK_UP_FWD if fwd else H.PACK_UP_DGRAD
+        bp = ops.k2_pack(w.to(dev), Cin, Cout, pk)
+        assert tuple(bp.shape) == tuple(shapes[1]), (tag, bp.shape)
+        if kind == 2:
+            wm = w.double()[:, :, 0, 0]
+            wm = wm.t() if fwd else wm                                   # [Cx, Co]
+            ref, cond = x.double() @ wm, x.double().abs() @ wm.abs()
+        else:
+            f64 = down64 if kind == 0 else up64
+            ref, cond = f64(x, w), f64(x.abs(), w.abs())
+        if b is not None:
+            ref, cond = ref + b.double(), cond + b.double().abs()
+        ys = tuple(ref.shape)
+        kw = {}
+        if "out" in flags:
+            out0 = gradient(g, ys)
+            kw["out"] = out0.clone().to(dev)
+            if acc:
+                kw["accumulate"] = True
+                ref, cond = ref + out0.double(), cond + out0.double().abs()
+        else:
+            assert not acc, tag
+        if op == "k2_fwd_stats":
+            G = ints[2]
+            rows = ops.k2_stat_rows(kind, xs, Co, G)
+            assert rows > 0 or dev.type == "cpu", f"{tag}: no fused statistics at the step's shape"
+            plain = ops.down_fwd if kind == 0 else ops.up_fwd
+            if rows:
+                y0 = plain(xd, bp, bd, Co).clone()
+                res, part, nb = ops.k2_fwd_stats(kind, xd, bp, bd, Co, G)
+                assert nb == rows and torch.equal(res, y0), f"{tag}: y differs from the plain launch"
+                pt = _partials(part, G, rows, Co)
+                yg = res.cpu().double().reshape(G, -1, Co)
+                worst = 0.0
+                for j, (s_, c) in enumerate(((yg.sum(1), yg.abs().sum(1)), ((yg * yg).sum(1), (yg * yg).sum(1)))):
+                    r = float(((pt[..., j] - s_).abs() / c.clamp_min(1e-300)).max())
+                    print(f"[product-op] {tag}: fused statistics partial {j} off by {r:.3e} x sum|.| ({rows} rows)")
+                    worst = max(worst, r)
+                assert worst <= TAU_K2_STATS, f"{tag}: fused statistics partials off by {worst:.3e} x sum|.| (bound {TAU_K2_STATS:.3e})"
+            else:
+                res = plain(xd, bp, bd, Co)
+        elif fwd or op == "pw_fwd":
+            res = getattr(ops, op)(xd, bp, bd, Co, **kw)
+        else:
+            res = getattr(ops, op)(xd, bp, Co, **kw)
+        out.append((name, check_elementwise(res.cpu(), ref, cond, TAU, tag, tile)))
+    return out
+
+
+def _raw_slabs(ops, dev, g, ys, nslab, x, fwd, tag):
+    """the split-K slabs of a real conv3_fwd_raw launch (C -> C) on x at the row's shape, with the forward (activation x) or the dgrad
+    (gradient x) pack -> (slabs on the device, float64 copy).  On the device the launch must write the key's slab count; the simulator's
+    reduced shapes may not be served raw, there the conv's output is split into `nslab` signed parts"""
+    from bcp_amd import hip_ops as H
+    C = ys[-1]
+    KD = 1 if ys[1] == 1 else 3
+    w = _conv_weight(g, C, C, KD)
+    wf, wd = ops.conv3_pack(w.to(dev), KD)
+    xd = _amax(H, x.to(dev), dev)
+    nsl = ops.conv3_nslabs(ys, C, KD)
+    assert nsl == nslab or dev.type == "cpu", f"{tag}: {nsl} split-K slabs, the step launches {nslab}"
+    if nsl == nslab:
+        slabs = ops.conv3_fwd_raw(xd, wf if fwd else wd, C, KD, nsl)
+    else:
+        y = ops.conv3_fwd(xd, wf if fwd else wd, None, C, KD)
+        parts = torch.randn((nslab - 1,) + tuple(ys), generator=g).to(dev) * y.abs().mean()
+        slabs = torch.cat([parts, (y - parts.sum(0)).unsqueeze(0)]).contiguous()
+    return slabs, slabs.cpu().double()
+
+
+def drive_norm_slabs(ops, dev, key, g, variants=((),)):
+    """norm_fwd_slabs / norm_bwd_slabs: the statistics pass sums the raw split-K slabs of a real conv3_fwd_raw launch (+ the conv bias)
+    on its way in and writes the sum once.  Reference: the fp64 sum of the slabs fed to the fp64 norm references; the written sum
+    (y, resp. da) against it elementwise; the epilogues of `variants` as in drive_norm_fwd / drive_norm_bwd"""
+    op, shapes, ints, namax = key
+    nslab, G, act = ints
+    fwd = op == "norm_fwd_slabs"
+    ys = tuple(shapes[0][1:] if fwd else shapes[0])
+    assert tuple((shapes[0] if fwd else shapes[1])) == (nslab,) + ys, key
+    C, N = ys[-1], ys[0]
+    tile = (1, 16, 16) if ys[1] == 1 else (4, 8, 8)
+    out = []
+    for flags in variants:
+        tag = f"{op} {ys} x{nslab} [{'+'.join(flags) or 'plain'}]"
+        name = op + ("" if not flags else " " + "+".join(flags))
+        if fwd:
+            affine = len(shapes) > 2
+            slabs, s64 = _raw_slabs(ops, dev, g, ys, nslab, activation(g, ys), True, tag)
+            bias = torch.randn(C, generator=g) * 0.1
+            gam = (torch.rand(C, generator=g) + 0.5) if affine else None
+            bet = (torch.rand(C, generator=g) - 0.5) if affine else None
+            rm0, rv0 = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
+            rm, rv = (rm0.clone().to(dev), rv0.clone().to(dev)) if affine else (None, None)
+            cs, sm, es, res, mult, H = _epilogue(ops, dev, g, ys, flags)
+            a, st, y = ops.norm_fwd_slabs(slabs, nslab, bias.to(dev), G, *((gam.to(dev), bet.to(dev)) if affine else (None, None)), rm, rv, act,
+                                          chan_scale=None if cs is None else cs.to(dev), elem_mask=sm, elem_scale=es,
+                                          residual=None if res is None else res.to(dev))
+            y64 = s64.sum(0) + bias.double()
+            out.append((name + " y", check_elementwise(y.cpu(), y64, s64.abs().sum(0) + bias.double().abs(), TAU, tag + " slab sum", tile)))
+            ar, z, xh, mu, var, _ = norm_ref64(y64, G, gam, bet, act)
+            _stats_check(st, mu, var, tag)
+            # cond composed as the op is: xhat = (sum of slabs + bias - mean) * rstd, each term by its magnitude (>= norm_ref64's own cond)
+            S = (s64.abs().sum(0) + bias.double().abs()).reshape(G, -1, C)
+            gm = torch.ones(C, dtype=torch.float64) if gam is None else gam.double().abs()
+            cond = (gm * ((S + mu.abs()) / torch.sqrt(var + EPS) + 1) + (0 if bet is None else bet.double().abs())).reshape(ys)
+            ref = ar * mult + (0 if res is None else res.double())
+            cnd = cond * mult.abs() + (0 if res is None else res.double().abs())
+            out.append((name, check_elementwise(a.cpu(), ref, cnd, TAU, tag, tile)))
+            if rm is not None:
+                _running_check(tag, rm, rv, rm0, rv0, mu, var, y64.numel() // C // G)
+            continue
+        accumulate = "accumulate" in flags
+        affine = accumulate or G != N
+        y = _pre_norm(g, ys)
+        gam = (torch.rand(C, generator=g) + 0.5) if affine else None
+        bet = (torch.rand(C, generator=g) - 0.5) if affine else None
+        yd = y.to(dev)
+        _, st = ops.norm_fwd(yd, G, *((gam.to(dev), bet.to(dev), torch.zeros(C, device=dev), torch.ones(C, device=dev)) if affine else (None,) * 4), act)
+        cs, sm, es, _, mult, H = _epilogue(ops, dev, g, ys, flags)
+        slabs, s64 = _raw_slabs(ops, dev, g, ys, nslab, gradient(g, ys), False, tag)
+        da64 = s64.sum(0)
+        ref, _, dz, xg, _ = _norm_bwd_ref64(y, G, gam, bet, act, da64, mult)
+        # cond composed as the op is: the kernel forms da in fp32 from the slabs, so the bound is the norm backward's on sum |slab|
+        _, cond, dzb, _, dk = _norm_bwd_ref64(y, G, gam, bet, act, s64.abs().sum(0), mult.abs())
+        dg0, db0 = (torch.randn(C, generator=g) * 1e-2, torch.randn(C, generator=g) * 1e-2) if accumulate else (torch.zeros(C), torch.zeros(C))
+        dg, db = (dg0.clone().to(dev), db0.clone().to(dev)) if affine else (None, None)
+        dy, da = ops.norm_bwd_slabs(yd, slabs, nslab, G, st, act, dg, db, accumulate, chan_scale=None if cs is None else cs.to(dev),
+                                    elem_mask=sm, elem_scale=es)
+        out.append((name + " da", check_elementwise(da.cpu(), da64, s64.abs().sum(0), TAU, tag + " slab sum", tile)))
+        out.append((name, check_elementwise(dy.cpu(), ref, cond, TAU, tag, tile)))
+        if affine:
+            _dgamma_dbeta_check(tag, dg, db, dg0, db0, dz, xg, dk, dzb)
+    return out
+
+
+def _boxes(sp, g):
+    """two boxes (d, h, w, size_d, size_h, size_w) of context_mask's size rule (2/3 of each extent) in a volume of extents sp: one at a
+    random position; one pushed against the three far faces, its sizes trimmed until neither they nor its origin are multiples of 4"""
+    size = [max(1, int(e * 2 / 3)) if e > 1 else 1 for e in sp]
+    rnd = tuple(int(torch.randint(0, e - s + 1, (1,), generator=g)) for e, s in zip(sp, size))
+    odd = list(size)
+    for i, e in enumerate(sp):
+        while e > 4 and (odd[i] % 4 == 0 or (e - odd[i]) % 4 == 0):
+            odd[i] -= 1
+    return rnd + tuple(size), tuple(e - s for e, s in zip(sp, odd)) + tuple(odd)
+
+
+def _in_box(sp, box6):
+    m = torch.zeros(sp, dtype=torch.bool)
+    d, h, w, sd, sh, sw = box6
+    m[d:d + sd, h:h + sh, w:w + sw] = True
+    return m
+
+
+def drive_mix_box(ops, dev, key, g, variants=((),)):
+    """mix_box at the step's shape, bit for bit against torch.where on the box, for a random box and one against three faces with ragged
+    edges; then with NaN in b outside the box and in a inside it: the kernel reads b inside the box only, a outside only"""
+    op, shapes, ints, namax = key
+    xs = shapes[0]
+    sp = tuple(xs[1:4])
+    out = []
+    for flags in variants:
+        for bi, box6 in enumerate(_boxes(sp, g)):
+            tag = f"{op} {xs} box {box6} [{'+'.join(flags) or 'plain'}]"
+            a, b = activation(g, xs), activation(g, xs) + 3.0
+            inb = _in_box(sp, box6).view((1,) + sp + (1,)).expand(xs)
+            ref = torch.where(inb, b, a)
+            nan = torch.full(xs, float("nan"))
+            for poison in (False, True):
+                ad, bd = (torch.where(inb, nan, a), torch.where(inb, b, nan)) if poison else (a, b)
+                kw = {"out": torch.full(xs, -1.0, device=dev)} if "out" in flags else {}
+                o = ops.mix_box(ad.to(dev), bd.to(dev), box6, **kw).cpu()
+                assert not bool(torch.isnan(o).any()), f"{tag}: read outside its side of the box (NaN in the output)"
+                assert torch.equal(o.view(torch.int32), ref.view(torch.int32)), f"{tag}: {int((o != ref).sum())} voxels differ from torch.where"
+            out.append((f"{op} box{bi}", (0.0, "exact")))
+    return out
+
+
+_NETS = {}
+
+
+def _step_network(wl, dev, ops):
+    """the workload's student network as its factory builds it for make_step (net_factory / BCP_net / create_Vnet), on `dev`, bound to `ops`"""
+    net = _NETS.get((wl, dev.type))
+    if net is None:
+        torch.manual_seed(1337)
+        if wl == "la":
+            from bcp_amd.networks.VNet import VNet
+            net = VNet(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True)
+        elif wl == "acdc":
+            from bcp_amd.networks.unet import UNet_2d
+            net = UNet_2d(in_chns=1, class_num=4)
+        else:
+            from bcp_amd.pancreas.Vnet import VNet
+            net = VNet()
+        net = _NETS[(wl, dev.type)] = net.to(dev).flatten_()
+    return net.set_ops(ops)
+
+
+def drive_pack_many(ops, dev, key, g, wl):
+    """conv3_pack_many / k2_pack_many: the network's own pack call (every layer in one launch, forward packs or forward + dgrad) over
+    poisoned buffers; every layer's packed buffer bit for bit against the single-layer conv3_pack / k2_pack of the same weight -- the conv
+    and GEMM drivers hold those single packs to fp64 through their consumers.  (descriptor bytes, n) must be the table's key."""
+    op, shapes, ints, namax = key
+    net = _step_network(wl, dev, ops)
+    c3 = op == "conv3_pack_many"
+    net._ensure_packed(False)                          # (builds the descriptor tables)
+    layers = net._c3 if c3 else net._k2
+    n = ints[0]
+    assert n in (len(layers), 2 * len(layers)), f"{op}: the step packs {n} descriptors, the network has {len(layers)} layers"
+    both = n == 2 * len(layers)
+    desc = (net._desc_all if both else net._desc_fwd) if c3 else (net._k2_desc_all if both else net._k2_desc_fwd)
+    assert tuple(desc.shape) == tuple(shapes[0]), f"{op}: descriptor table of {tuple(desc.shape)} bytes, the step's has {shapes[0]}"
+    with torch.no_grad():                               # new weights, so that packs left by an earlier row cannot pass
+        for w in (l[1] for l in layers):
+            w.mul_(1.0 + 0.25 * float(torch.rand(1, generator=g)))
+    (net._pack_buf if c3 else net._k2_buf).fill_(float("nan"))
+    net._pack_state = net._k2_state = None
+    net._ensure_packed(both)
+    bad = []
+    for l in layers:
+        if c3:
+            k, w, KD = l
+            single = ops.conv3_pack(w.data, KD)
+            views = net._pack_views[k]
+        else:
+            k, w, Cin, Cout, kf, kd = l
+            single = (ops.k2_pack(w.data, Cin, Cout, kf), ops.k2_pack(w.data, Cin, Cout, kd))
+            views = net._k2_views[k]
+        for d in range(2 if both else 1):
+            a, b = views[d].view(torch.int32), single[d].view(torch.int32)
+            if c3:
+                # the pack ends in a 32-word header: word 0 the weight's |max| (what the convs read), words 1 .. 16 the pack kernels' partial
+                # maxima -- scratch, which a dgrad descriptor behind its forward twin leaves to the twin's header (csrc/conv3.hip k_wamax_many)
+                h = a.numel() - 32
+                a, b = torch.cat([a[:h + 1], a[h + 17:]]), torch.cat([b[:h + 1], b[h + 17:]])
+            if not torch.equal(a, b):
+                bad.append((k, "dgrad" if d else "fwd", int((a != b).sum())))
+    assert not bad, f"{op} {n}: packed buffers differ from the single-layer pack: {bad[:6]}"
+    return [(f"{op} {len(layers)} layers", (0.0, "exact"))]
+
+
+def drive_c1(ops, dev, key, g, variants=((),)):
+    """the fused first layer.  conv3_c1_norm_fwd: a = act(norm(conv(x, w) + b)) with y recomputed in fp32 and never stored, so cond is the
+    norm's plus |gamma| * rstd * conv(|x|, |w|); statistics and running statistics as drive_norm_fwd.  conv3_c1_norm_bwd_wgrad: dw =
+    wgrad(x, dy) with dy the fp64 norm backward (never written by the kernel), dgamma / dbeta as drive_norm_bwd; the flags (accumulate,
+    dw_accumulate, the seeded dropout mask) are the step's.  The key does not say whether the norm is affine: the forward runs BatchNorm
+    and, where G == N, InstanceNorm; the backward is affine where the step accumulates dgamma / dbeta."""
+    op, shapes, ints, namax = key
+    xs, ws = shapes[0], shapes[1]
+    KD, G, act = ints
+    two_d = KD == 1
+    N, C = xs[0], 16
+    ys = tuple(xs[:-1]) + (C,)
+    tile = (1, 16, 16) if two_d else (4, 8, 8)
+    fwd = op == "conv3_c1_norm_fwd"
+    assert ops.conv3_c1_norm_ok(xs, KD, G), f"{op} {xs}: the fused first layer does not serve the step's shape"
+    out = []
+    for flags in variants:
+        for affine in ((True, False) if G == N else (True,)) if fwd else ("accumulate" in flags or G != N,):
+            tag = f"{op} {xs} [{'+'.join(flags) or 'plain'}{'' if affine else ' instance'}]"
+            name = op + ("" if not flags else " " + "+".join(flags)) + ("" if affine else " in")
+            x = activation(g, xs)
+            w = _conv_weight(g, C, 1, KD)
+            assert tuple(w.shape) == tuple(ws), key
+            b = torch.randn(C, generator=g) * 0.1
+            gam = (torch.rand(C, generator=g) + 0.5) if affine else None
+            bet = (torch.rand(C, generator=g) - 0.5) if affine else None
+            rm0, rv0 = torch.randn(C, generator=g) * 0.1, torch.rand(C, generator=g) + 0.5
+            rm, rv = (rm0.clone().to(dev), rv0.clone().to(dev)) if affine else (None, None)
+            _, sm, es, _, mult, H = _epilogue(ops, dev, g, ys, flags)
+            xd, wd, bd = x.to(dev), w.to(dev), b.to(dev)
+            a, st = ops.conv3_c1_norm_fwd(xd, wd, bd, KD, G, *((gam.to(dev), bet.to(dev)) if affine else (None, None)), rm, rv, act,
+                                          elem_mask=sm, elem_scale=es)
+            y64 = conv3_cl64(x, w) + b.double()
+            cy = conv3_cl64(x.abs(), w.abs()) + b.double().abs()
+            ar, z, xh, mu, var, ncond = norm_ref64(y64, G, gam, bet, act)
+            gm = torch.ones(C, dtype=torch.float64) if gam is None else gam.double().abs()
+            ycond = (gm / torch.sqrt(var + EPS) * cy.reshape(G, -1, C)).reshape(ys)       # what the fp32 recompute of y can move z by, per unit
+            if fwd:
+                _stats_check(st, mu, var, tag)
+                out.append((name, check_elementwise(a.cpu(), ar * mult, (ncond + ycond) * mult.abs(), TAU, tag, tile)))
+                if rm is not None:
+                    _running_check(tag, rm, rv, rm0, rv0, mu, var, y64.numel() // C // G)
+                continue
+            da = gradient(g, ys)
+            acc, dwacc = "accumulate" in flags, "dw_accumulate" in flags
+            dy, dcond, dz, xg, dk = _norm_bwd_ref64(y64, G, gam, bet, act, da.double(), mult, ycond)
+            wg = conv3_wgrad64(x, dy, 3, two_d)
+            dw0 = gradient(g, ws, -4.0, 0.0) if dwacc else torch.zeros(ws)
+            dg0, db0 = (torch.randn(C, generator=g) * 1e-2, torch.randn(C, generator=g) * 1e-2) if acc else (torch.zeros(C), torch.zeros(C))
+            dg, db = (dg0.clone().to(dev), db0.clone().to(dev)) if affine else (None, None)
+            dwd = dw0.clone().to(dev) if dwacc else torch.full(ws, float("nan"), device=dev)
+            ops.conv3_c1_norm_bwd_wgrad(xd, wd, bd, KD, G, st, da.to(dev), act, dwd, dg, db, acc, dw_accumulate=dwacc, elem_mask=sm, elem_scale=es)
+            # a kink element may take either branch: its own term and its share of the two means, through |x|, are allowed on top of the bound
+            rstd = (gm / torch.sqrt(var + EPS))
+            kdy = (rstd * (dk + dk.mean(1, keepdim=True) + xg.abs() * (dk * xg.abs()).mean(1, keepdim=True))).reshape(ys)
+            dcond = torch.where(torch.isinf(dcond), torch.zeros_like(dcond), dcond)
+            ref = wg + dw0.double()
+            cond = conv3_wgrad64(x.abs(), dcond, 3, two_d) + dw0.double().abs()
+            allow = conv3_wgrad64(x.abs(), kdy, 3, two_d)
+            err = ((dwd.cpu().double() - ref).abs() - allow).clamp_min(0)
+            out.append((name, check_elementwise(err, torch.zeros_like(err), cond, TAU, tag)))
+            if affine:
+                _dgamma_dbeta_check(tag, dg, db, dg0, db0, dz, xg, dk)
+    return out
+
+
+def drive_head(ops, dev, key, g, variants=((),)):
+    """the fused 16 -> C head.  pw16_fwd_norm: logits = (act(norm(y)) * chan_scale) @ W^T + b from the raw conv output and the
+    statistics of a real norm_fwd(stats_only) fed by conv3_fwd_stats partials, as the network runs it.  pw16_bwd_norm_bwd: dw / db of the
+    head, dgamma / dbeta of the norm as bounded sums, the returned gradient w.r.t. y elementwise.  BatchNorm where the step passes a
+    channel scale or accumulates the norm's gradients (LA), InstanceNorm otherwise (pancreas); the forward runs both."""
+    op, shapes, ints, namax = key
+    ys = shapes[0]
+    G, act = ints[0], ints[1]
+    N, C, Cout = ys[0], ys[-1], 2
+    fwd = op == "pw16_fwd_norm"
+    assert not fwd or ints[2] == Cout, key
+    out = []
+    for flags in variants:
+        for affine in ((True, False) if G == N else (True,)) if fwd else ("norm_accumulate" in flags or G != N,):
+            tag = f"{op} {ys} [{'+'.join(flags) or 'plain'}{'' if affine else ' instance'}]"
+            name = op + ("" if not flags else " " + "+".join(flags)) + ("" if affine else " in")
+            yd, part, rows = _conv_partial_source(ops, dev, g, ys, G)
+            assert rows > 0 or dev.type == "cpu", f"{tag}: conv3_fwd_stats left no partials at the step's shape"
+            y = yd.cpu()
+            gam = (torch.rand(C, generator=g) + 0.5) if affine else None
+            bet = (torch.rand(C, generator=g) - 0.5) if affine else None
+            rm, rv = (torch.zeros(C, device=dev), torch.ones(C, device=dev)) if affine else (None, None)
+            cs, _, _, _, mult, H = _epilogue(ops, dev, g, ys, tuple(f for f in flags if f == "chan_scale"))
+            csd = None if cs is None else cs.to(dev)
+            _, st = ops.norm_fwd(yd, G, *((gam.to(dev), bet.to(dev)) if affine else (None, None)), rm, rv, act, chan_scale=csd, stats_only=True,
+                                 **({"partial": part, "nb": rows} if rows else {}))
+            w = _k2_weight(g, (Cout, C, 1, 1, 1), C)
+            b = torch.randn(Cout, generator=g) * 0.1
+            wd, bd = w.to(dev), b.to(dev)
+            W = w.double().reshape(Cout, C)
+            ar, z, xh, mu, var, ncond = norm_ref64(y, G, gam, bet, act)
+            _stats_check(st, mu, var, tag)
+            if fwd:
+                lg = ops.pw16_fwd_norm(yd, st, csd, G, act, wd, bd, Cout)
+                ref = (ar * mult) @ W.t() + b.double()
+                cond = (ncond * mult.abs()) @ W.abs().t() + b.double().abs()
+                out.append((name, check_elementwise(lg.cpu(), ref, cond, TAU, tag)))
+                continue
+            acc, nacc = "accumulate" in flags, "norm_accumulate" in flags
+            dy = gradient(g, tuple(ys[:-1]) + (Cout,))
+            d2 = dy.double().reshape(-1, Cout)
+            a2, c2 = (ar * mult).reshape(-1, C), (ncond * mult.abs()).reshape(-1, C)
+            dwr, dcr = d2.t() @ a2, d2.sum(0)
+            dw0, dc0 = (gradient(g, tuple(w.shape), -4.0, 0.0), gradient(g, (Cout,), -4.0, 0.0)) if acc else (torch.zeros(w.shape), torch.zeros(Cout))
+            dg0, db0 = (torch.randn(C, generator=g) * 1e-2, torch.randn(C, generator=g) * 1e-2) if nacc else (torch.zeros(C), torch.zeros(C))
+            dwd, dcd = ((dw0.clone().to(dev), dc0.clone().to(dev)) if acc
+                        else (torch.full(tuple(w.shape), float("nan"), device=dev), torch.full((Cout,), float("nan"), device=dev)))
+            dg, db = (dg0.clone().to(dev), db0.clone().to(dev)) if affine else (None, None)
+            dyr = ops.pw16_bwd_norm_bwd(yd, st, csd, G, act, dy.to(dev), wd, dwd, dcd, dg, db, norm_accumulate=nacc, accumulate=acc)
+            out.append((name + " dw", check_elementwise(dwd.cpu().reshape(Cout, C), dwr + dw0.double().reshape(Cout, C),
+                                                        d2.abs().t() @ c2 + dw0.double().abs().reshape(Cout, C), TAU, tag + " dw")))
+            out.append((name + " db", check_elementwise(dcd.cpu(), dcr + dc0.double(), d2.abs().sum(0) + dc0.double().abs(), TAU, tag + " db")))
+            # the gradient entering the norm is dy @ W, formed in fp32: the bound is the norm backward's on |dy| @ |W|
+            ref, _, dz, xg, _ = _norm_bwd_ref64(y, G, gam, bet, act, dy.double() @ W, mult)
+            _, cond, dzb, _, dk = _norm_bwd_ref64(y, G, gam, bet, act, dy.double().abs() @ W.abs(), mult.abs())
+            out.append((name, check_elementwise(dyr.cpu(), ref, cond, TAU, tag)))
+            if affine:
+                _dgamma_dbeta_check(tag, dg, db, dg0, db0, dz, xg, dk, dzb)
+    return out
+
+
+def mixloss_pair64(logits, labs, box6, flavour, weights, dtype=torch.float64):
+    """closed form of the step's two mix_loss calls on channels-last logits [2N, D, H, W, C]: call h on samples hN .. hN + N - 1 with labels
+    labs[h] = (img_l, patch_l) [N, D, H, W] and weights[h] = (w_img, w_patch); the image term outside the box, the patch term inside.
+    flavour 0 (LA / pancreas, C = 2): masked soft Dice per (sample, class), smooth 1e-5, mean over N * C; loss = (dice + ce) / 2, out3 =
+    {loss, ce, dice}, total = loss_1 + loss_2.  flavour 1 (ACDC, C = 4): Dice per class over the batch with squared denominators, smooth
+    1e-10, mean over classes; out3 = {dice, ce, (dice + ce) / 2}, total = ((dice_2 + dice_1) + (ce_2 + ce_1)) / 2.  CE: region sum
+    over region count + 1e-16.  -> (out6 [2, 3], total, d total / d logits, cond of that gradient: the sum of its terms' magnitudes),
+    evaluated in `dtype` throughout (fp64: the reference; fp32: what plain fp32 arithmetic makes of the same expression)"""
+    L = logits.to(dtype)
+    N2, C = L.shape[0], L.shape[-1]
+    N = N2 // 2
+    sp = tuple(L.shape[1:4])
+    inb = _in_box(sp, box6).reshape(1, -1)
+    p = torch.softmax(L.reshape(N2, -1, C), dim=-1)
+    lse = torch.logsumexp(L.reshape(N2, -1, C), dim=-1)
+    out6 = torch.zeros(2, 3, dtype=dtype)
+    grad, cond = torch.zeros_like(p), torch.zeros_like(p)
+    for h in range(2):
+        ph, Lh = p[h * N:(h + 1) * N], L.reshape(N2, -1, C)[h * N:(h + 1) * N]
+        gp, gpa = torch.zeros_like(ph), torch.zeros_like(ph)            # d / d p of the dice term, and the magnitudes of its terms
+        gl, gla = torch.zeros_like(ph), torch.zeros_like(ph)            # d / d logits of the ce term
+        dice = ce = torch.zeros((), dtype=dtype)
+        for lab, wgt, reg in ((labs[h][0], weights[h][0], ~inb), (labs[h][1], weights[h][1], inb)):
+            r = reg.to(dtype).expand(N, -1).unsqueeze(-1)               # [N, V, 1]
+            t = torch.nn.functional.one_hot(lab.reshape(N, -1).long(), C).to(dtype)
+            if flavour == 0:
+                s = 1e-5
+                I, U = (ph * t * r).sum(1, keepdim=True), ((ph + t) * r).sum(1, keepdim=True)
+                dice = dice + wgt * (1 - ((2 * I + s) / (U + s)).mean())
+                k = wgt / (N * C) / (U + s) ** 2
+                gp = gp - k * r * (2 * t * (U + s) - (2 * I + s))
+                gpa = gpa + k * r * (2 * t * (U + s) + (2 * I + s))
+            else:
+                s = 1e-10
+                I, Y, Z = (ph * t * r).sum((0, 1), keepdim=True), (t * r).sum((0, 1), keepdim=True), (ph * ph * r).sum((0, 1), keepdim=True)
+                dice = dice + wgt * (1 - (2 * I + s) / (Z + Y + s)).sum() / C
+                k = wgt / C / (Z + Y + s) ** 2
+                gp = gp - k * r * (2 * t * (Z + Y + s) - (2 * I + s) * 2 * ph)
+                gpa = gpa + k * r * (2 * t * (Z + Y + s) + (2 * I + s) * 2 * ph)
+            cnt = r.sum() + 1e-16
+            ce = ce + wgt * ((lse[h * N:(h + 1) * N].unsqueeze(-1) * t - Lh * t).sum(-1, keepdim=True) * r).sum() / cnt
+            gl = gl + wgt / cnt * r * (ph - t)
+            gla = gla + wgt / cnt * r * (ph + t)
+        out6[h] = torch.stack([(dice + ce) / 2, ce, dice] if flavour == 0 else [dice, ce, (dice + ce) / 2])
+        # softmax Jacobian on the dice part: dL_c = p_c * (gp_c - sum_k p_k gp_k); every term by its magnitude in cond
+        dot, dota = (ph * gp).sum(-1, keepdim=True), (ph * gpa).sum(-1, keepdim=True)
+        grad[h * N:(h + 1) * N] = 0.5 * (ph * (gp - dot) + gl)
+        cond[h * N:(h + 1) * N] = 0.5 * (ph * (gpa + dota) + gla)
+    total = out6[0, 0] + out6[1, 0] if flavour == 0 else ((out6[1, 0] + out6[0, 0]) + (out6[1, 1] + out6[0, 1])) / 2
+    return out6, total, grad.reshape(L.shape), cond.reshape(L.shape)
+
+
+# d total / d logits against the fp64 closed form, in units of cond (the sum of the closed form's term magnitudes).  The same closed form
+# evaluated in fp32 by torch on the host differs from fp64 by at most TAU_LOSS_TORCH32 x cond over the drivers' inputs (all rows, both
+# boxes); TAU_LOSS = 4 x that, rounded up to a power of two -- the kernel may order its few roundings differently.  The kernel itself
+# measured TAU_LOSS_KERNEL x cond on the device.
+TAU_LOSS_TORCH32 = 1.30e-6      # = 21.7 x 2^-24 (ACDC 12 x 256 x 256 x 4; LA 1.13e-6, pancreas 1.10e-6): exp() of a logit difference up to 24
+TAU_LOSS_KERNEL = 1.24e-6       # ACDC, box against three faces; LA 1.07e-6, pancreas 1.09e-6; the simulator at the reduced LA shape 1.03e-6
+TAU_LOSS = 2.0 ** -17           # 4 x 1.30e-6 = 5.2e-6 -> 7.63e-6
+
+
+def _loss_inputs(g, ls, C):
+    """logits spread over +-12 (some softmaxes saturate), blob-structured labels (cc_maps' smoothed noise, classes in bands for C = 4)"""
+    N2 = ls[0]
+    N, sp = N2 // 2, tuple(ls[1:4])
+    logits = ((torch.rand(ls, generator=g, dtype=torch.float64) * 2 - 1) * 12).float()
+    labs = []
+    for _ in range(4):
+        m = cc_maps((N,) + sp, g, two_d=sp[0] == 1)[0][1].long()
+        if C == 4:
+            m = (m * (1 + (torch.arange(sp[2]) * 3 // max(sp[2], 1)).view(1, 1, 1, -1))).clamp(max=3)
+        labs.append(m.to(torch.uint8).contiguous())
+    return logits, ((labs[0], labs[1]), (labs[2], labs[3]))
+
+
+def drive_mixloss(ops, dev, key, g, variants=((),)):
+    """mixloss_pair_fwd / mixloss_pair_bwd at the step's shape against the fp64 closed form (mixloss_pair64), for a random box and one
+    against three faces with ragged edges: out6 and total to the project's gate |d| <= 1e-5, the gradient elementwise to TAU_LOSS x cond.
+    The backward runs as the step's: written into a given buffer, the upstream gradient read from the device."""
+    op, shapes, ints, namax = key
+    ls, flavour = shapes[0], ints[0]
+    C = ls[-1]
+    sp = tuple(ls[1:4])
+    weights = ((1.0, 0.5), (0.5, 1.0))                  # (labeled image + unlabeled patch, then the reverse: l_weight 1, u_weight 0.5)
+    tile = (1, 16, 16) if sp[0] == 1 else (4, 8, 8)
+    out = []
+    for flags in variants:
+        for bi, box6 in enumerate(_boxes(sp, g)):
+            tag = f"{op} {ls} box {box6} [{'+'.join(flags) or 'plain'}]"
+            logits, labs = _loss_inputs(g, ls, C)
+            o64, t64, g64, c64 = mixloss_pair64(logits, labs, box6, flavour, weights)
+            ld = logits.to(dev)
+            lab = [t.to(dev) for pair in labs for t in pair]
+            o6, total, ws = ops.mixloss_pair_fwd(ld, lab[0], lab[1], lab[2], lab[3], box6, flavour, weights[0], weights[1])
+            d6 = float((o6.cpu().double() - o64).abs().max())
+            dt = float((total.cpu().double() - t64).abs().max())
+            print(f"[product-op] {tag}: out6 off by {d6:.3e} (relative {float(((o6.cpu().double() - o64).abs() / o64.abs()).max()):.3e}), "
+                  f"total by {dt:.3e} (relative {dt / float(t64.abs()):.3e})")
+            assert d6 <= 1e-5 and dt <= 1e-5, f"{tag}: out6 off by {d6:.3e}, total by {dt:.3e}"
+            if op == "mixloss_pair_fwd":
+                out.append((f"{op} box{bi}", (max(d6, dt) / 1e-5, "scalars")))
+                continue
+            up = 0.75
+            kw = {}
+            if "out" in flags:
+                kw["out"] = torch.full(ls, float("nan"), device=dev)
+            if "g_dev" in flags:
+                kw["g_dev"] = torch.full((1,), up, device=dev)
+            d = ops.mixloss_pair_bwd(ld, lab[0], lab[1], lab[2], lab[3], box6, flavour, ws, 0.5 * (1.0 if "g_dev" in flags else up),
+                                     0.5 * (1.0 if "g_dev" in flags else up), **kw)
+            _, _, g32, _ = mixloss_pair64(logits, labs, box6, flavour, weights, torch.float32)
+            r32, _ = elementwise_ratio(g32.double(), g64, c64)
+            print(f"[product-op] {tag}: the closed form in torch fp32 is off by {r32:.3e} x cond ({r32 / 2.0 ** -24:.2f} x 2^-24)")
+            res = check_elementwise(d.cpu(), up * g64, up * c64, TAU_LOSS, tag, tile)
+            print(f"[product-op] {tag}: the kernel is off by {res[0] * TAU_LOSS:.3e} x cond")
+            out.append((f"{op} box{bi}", res))
+    return out
+
+
 DRIVERS = {"conv3_fwd": drive_conv, "conv3_fwd_stats": drive_conv, "conv3_fwd_raw": drive_conv, "conv3_dgrad_bwdstats": drive_conv,
            "conv3_wgrad": drive_wgrad, "norm_fwd": drive_norm_fwd, "norm_bwd": drive_norm_bwd,
            "sgd": drive_optim, "ema": drive_optim, "adam": drive_optim,
            "maxpool2d_fwd": drive_pool, "maxpool2d_bwd": drive_pool, "bilinear2x_fwd": drive_pool, "bilinear2x_bwd": drive_pool,
-           "plabel_cc_largest": drive_cc}
+           "plabel_cc_largest": drive_cc,
+           "down_fwd": drive_k2, "down_dgrad": drive_k2, "up_fwd": drive_k2, "up_dgrad": drive_k2, "k2_fwd_stats": drive_k2,
+           "k2_wgrad": drive_k2, "pw_fwd": drive_k2, "norm_fwd_slabs": drive_norm_slabs, "norm_bwd_slabs": drive_norm_slabs,
+           "mix_box": drive_mix_box, "conv3_pack_many": drive_pack_many, "k2_pack_many": drive_pack_many,
+           "conv3_c1_norm_fwd": drive_c1, "conv3_c1_norm_bwd_wgrad": drive_c1, "pw16_fwd_norm": drive_head, "pw16_bwd_norm_bwd": drive_head,
+           "mixloss_pair_fwd": drive_mixloss, "mixloss_pair_bwd": drive_mixloss}
 
 
 def table_rows():
@@ -965,8 +1591,8 @@ def row_id(wl, key):
 
 
 def reduce_key(key, f=8):
-    """the key with every spatial extent divided by f (at least 2, even where a pool needs it) and flat sizes by f^3: the host
-    simulator's twin of an in-step shape"""
+    """the key with every spatial extent divided by f (at least 2, even where a pool or a stride-2 conv needs it) and flat sizes by
+    f^3: the host simulator's twin of an in-step shape"""
     op, shapes, ints, namax = key
 
     def red(s):
@@ -978,7 +1604,28 @@ def reduce_key(key, f=8):
         if len(s) == 1 and op in ("sgd", "ema", "adam"):
             return (max(64, s[0] // f ** 3),)
         return s
-    shapes = tuple(s if (i == 2 and op.endswith("wgrad")) else red(s) for i, s in enumerate(shapes))      # (a weight gradient's shape stays)
+    def fine(s):
+        """a k2s2 op's fine grid: every extent even, so that the coarse grid is exactly its half"""
+        N, D, H, W, C = s
+        return (N,) + tuple(max(2, e // f) // 2 * 2 for e in (D, H, W)) + (C,)
+
+    def coarse(s):
+        """the coarse grid of a k2s2 op, derived from its reduced fine grid (28 // 8 = 3 is no half of anything)"""
+        N, D, H, W, C = s
+        fs = fine((N, 2 * D, 2 * H, 2 * W, C))
+        return (N, fs[1] // 2, fs[2] // 2, fs[3] // 2, C)
+    # which of a k2s2 op's leading tensors live on the fine / coarse grid
+    grids = {"down_fwd": (fine,), "up_dgrad": (fine,), "down_dgrad": (coarse,), "up_fwd": (coarse,),
+             "k2_fwd_stats": ((fine,), (coarse,))[ints[0]] if op == "k2_fwd_stats" else None,
+             "k2_wgrad": ((fine, coarse), (coarse, fine), (red, red))[ints[0]] if op == "k2_wgrad" else None}.get(op)
+    if grids:
+        shapes = tuple(grids[i](s) if i < len(grids) else s for i, s in enumerate(shapes))
+        return op, shapes, ints, namax
+    # shapes that stay: a weight gradient's, and the weights behind the input of the fused first layer and head
+    first_only = op in ("conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm")
+    shapes = tuple(s if (i > 0 and first_only) or (i == 2 and op.endswith("wgrad")) else red(s) for i, s in enumerate(shapes))
+    if op == "mix_box":                     # (the kernel takes W * C in fours)
+        shapes = tuple(s[:3] + (max(4, s[3] // 4 * 4), s[4]) for s in shapes)
     if op in ("maxpool2d_bwd",):
         x = shapes[0]
         shapes = (x, (x[0], 1, x[2] // 2, x[3] // 2, x[4]), x)
@@ -992,27 +1639,36 @@ def reduce_key(key, f=8):
 # The profile key carries no keyword arguments, yet the norm kwargs pick different kernels (statistics from a conv's fused partials ->
 # finalize -> apply; the apply pass's channel-scale / dropout / residual epilogue; statistics only).  `record_step_variants` reads them
 # off the step itself: during the eager recording pass it notes, per key, which epilogue each norm call used.
-_VARIANT_OPS = ("norm_fwd", "norm_bwd")
+_VARIANT_OPS = ("norm_fwd", "norm_bwd", "down_fwd", "down_dgrad", "up_fwd", "up_dgrad", "k2_fwd_stats", "k2_wgrad", "pw_fwd",
+                "norm_fwd_slabs", "norm_bwd_slabs", "mix_box", "conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm",
+                "pw16_bwd_norm_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd")
+_FLAG_ORDER = ("chan_scale", "elem_mask", "partial", "residual", "stats_only", "out_slab", "accumulate", "dw_accumulate",
+               "norm_accumulate", "out", "mask", "g_dev")
 
 
 def _variant_flags(name, kw):
-    f = []
-    if kw.get("chan_scale") is not None:
-        f.append("chan_scale")
-    em = kw.get("elem_mask")
-    if em is not None:
-        f.append("elem_mask")
-    if kw.get("partial") is not None:
-        f.append("partial")
+    """the flags of one call; kw: its arguments by parameter name (inspect.signature(...).bind: the networks pass some positionally)"""
+    f = [n for n in ("chan_scale", "elem_mask", "partial") if kw.get(n) is not None]
+    if kw.get("residual") is not None:
+        f.append("residual")
+    if kw.get("stats_only"):
+        f.append("stats_only")
+    out = kw.get("out")
     if name == "norm_fwd":
-        if kw.get("residual") is not None:
-            f.append("residual")
-        if kw.get("stats_only"):
-            f.append("stats_only")
-        out = kw.get("out")
         if out is not None and out.dim() >= 2 and out.stride(-2) != out.shape[-1]:
             f.append("out_slab")
+        out = None
+    if name != "norm_bwd":                               # (norm_bwd's accumulate is the third int of its key already)
+        f += [n for n in ("accumulate", "dw_accumulate", "norm_accumulate") if kw.get(n)]
+    if out is not None:
+        f.append("out")
+    f += [n for n in ("mask", "g_dev") if kw.get(n) is not None]
     return tuple(f)
+
+
+def _bound(fn, self, a, kw):
+    import inspect
+    return inspect.signature(fn).bind(self, *a, **kw).arguments
 
 
 def variant_key(name, a):
@@ -1022,20 +1678,21 @@ def variant_key(name, a):
             sum(1 for t in ts[:2] if getattr(t, "_bcp_amax", None) is not None))
 
 
-def record_step_variants(workload):
-    """{key: set of epilogue flag tuples} of the norm calls of one step of `workload` (its eager recording pass)"""
+def record_step_variants(workload, names=None):
+    """{key: set of flag tuples} of the calls of the ops `names` (_VARIANT_OPS) in one step of `workload` (its eager recording pass)"""
     from bcp_amd.hip_ops import Ops
     seen = {}
-    saved = {n: getattr(Ops, n) for n in _VARIANT_OPS}
+    names = _VARIANT_OPS if names is None else names
+    saved = {n: getattr(Ops, n) for n in names}
 
     def wrap(name, fn):
         def w(self, *a, **kw):
             k = variant_key(name, a)
             k = (k[0], tuple(tuple(int(v) for v in s) for s in k[1]), tuple(int(v) for v in k[2]), k[3])
-            seen.setdefault(k, set()).add(_variant_flags(name, kw))
+            seen.setdefault(k, set()).add(_variant_flags(name, _bound(fn, self, a, kw)))
             return fn(self, *a, **kw)
         return w
-    for n in _VARIANT_OPS:
+    for n in names:
         setattr(Ops, n, wrap(n, saved[n]))
     try:
         step = make_step(workload, torch.device("cuda:0"))
@@ -1043,12 +1700,12 @@ def record_step_variants(workload):
             step()
         torch.cuda.synchronize()
     finally:
-        for n in _VARIANT_OPS:
+        for n in names:
             setattr(Ops, n, saved[n])
     return seen
 
 
-STEP_VARIANTS = {   # {workload: {norm key: epilogues the step uses}} (record_step_variants)
+STEP_VARIANTS = {   # {workload: {key: flag sets the step uses}} (record_step_variants)
     "la": {
         ('norm_bwd', ((2, 7, 7, 5, 256), (2, 7, 7, 5, 256), (5, 2, 256)), (2, 1, 1), 0): (('chan_scale',),),
         ('norm_bwd', ((2, 14, 14, 10, 128), (2, 14, 14, 10, 128), (5, 2, 128)), (2, 1, 1), 0): ((),),
@@ -1060,6 +1717,41 @@ STEP_VARIANTS = {   # {workload: {norm key: epilogues the step uses}} (record_st
         ('norm_fwd', ((2, 28, 28, 20, 64), (64,), (64,)), (2, 1), 0): ((), ('partial',), ('residual',)),
         ('norm_fwd', ((2, 56, 56, 40, 32), (32,), (32,)), (2, 1), 0): ((), ('partial',), ('residual',)),
         ('norm_fwd', ((2, 112, 112, 80, 16), (16,), (16,)), (2, 1), 0): (('chan_scale', 'partial', 'stats_only'), ('partial', 'residual')),
+        ('down_dgrad', ((2, 7, 7, 5, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 14, 14, 10, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 28, 28, 20, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 56, 56, 40, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('k2_wgrad', ((2, 7, 7, 5, 256), (2, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 112, 112, 80, 16), (2, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0): (('out',),),
+        ('norm_bwd_slabs', ((2, 7, 7, 5, 256), (8, 2, 7, 7, 5, 256), (5, 2, 256)), (8, 2, 1), 0): (('accumulate',),),
+        ('norm_bwd_slabs', ((2, 14, 14, 10, 128), (4, 2, 14, 14, 10, 128), (5, 2, 128)), (4, 2, 1), 0): (('accumulate',),),
+        ('norm_fwd_slabs', ((8, 2, 7, 7, 5, 256), (256,), (256,)), (8, 2, 1), 0): ((), ('chan_scale',)),
+        ('conv3_c1_norm_bwd_wgrad', ((2, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): (('accumulate', 'dw_accumulate'),),
+        ('pw16_bwd_norm_bwd', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1), 0): (('chan_scale', 'accumulate', 'norm_accumulate'),),
+        ('pw16_fwd_norm', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1, 2), 0): (('chan_scale',),),
+        ('mixloss_pair_bwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): (('out', 'g_dev'),),
+        ('conv3_c1_norm_fwd', ((2, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): ((),),
+        ('down_fwd', ((2, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((2, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((2, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((2, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('k2_fwd_stats', ((2, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 2), 1): ((),),
+        ('mixloss_pair_fwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): ((),),
+        ('norm_fwd_slabs', ((4, 2, 14, 14, 10, 128), (128,), (128,)), (4, 2, 1), 0): ((),),
+        ('up_dgrad', ((2, 14, 14, 10, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((2, 28, 28, 20, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((2, 56, 56, 40, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((2, 112, 112, 80, 16), (4096,)), (32,), 1): ((),),
+        ('up_fwd', ((2, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((2, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((2, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
     },
     "pancreas": {
         ('norm_bwd', ((2, 6, 6, 6, 256), (2, 6, 6, 6, 256), (5, 2, 256)), (2, 1, 0), 0): ((),),
@@ -1072,6 +1764,41 @@ STEP_VARIANTS = {   # {workload: {norm key: epilogues the step uses}} (record_st
         ('norm_fwd', ((2, 24, 24, 24, 64),), (2, 1), 0): ((), ('partial',), ('residual',)),
         ('norm_fwd', ((2, 48, 48, 48, 32),), (2, 1), 0): ((), ('partial',), ('residual',)),
         ('norm_fwd', ((2, 96, 96, 96, 16),), (2, 1), 0): (('partial', 'residual'), ('partial', 'stats_only')),
+        ('down_dgrad', ((2, 6, 6, 6, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 12, 12, 12, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 24, 24, 24, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 48, 48, 48, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('k2_wgrad', ((2, 6, 6, 6, 256), (2, 12, 12, 12, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 6, 6, 6, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 24, 24, 24, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 12, 12, 12, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 48, 48, 48, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 24, 24, 24, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 96, 96, 96, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 96, 96, 96, 16), (2, 48, 48, 48, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 96, 96, 96, 1), (1, 96, 96, 96, 1)), (), 0): (('out',),),
+        ('conv3_c1_norm_bwd_wgrad', ((2, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): (('dw_accumulate',),),
+        ('pw16_bwd_norm_bwd', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 96, 96, 96, 2)), (2, 1), 0): (('accumulate',),),
+        ('mixloss_pair_bwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): (('out', 'g_dev'),),
+        ('conv3_c1_norm_fwd', ((2, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): ((),),
+        ('down_fwd', ((2, 12, 12, 12, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((2, 24, 24, 24, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((2, 48, 48, 48, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((2, 96, 96, 96, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('k2_fwd_stats', ((2, 48, 48, 48, 32), (4096,), (16,)), (1, 16, 2), 1): ((),),
+        ('mixloss_pair_fwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): ((),),
+        ('norm_bwd_slabs', ((2, 6, 6, 6, 256), (8, 2, 6, 6, 6, 256), (5, 2, 256)), (8, 2, 1), 0): ((),),
+        ('norm_bwd_slabs', ((2, 12, 12, 12, 128), (4, 2, 12, 12, 12, 128), (5, 2, 128)), (4, 2, 1), 0): ((),),
+        ('norm_fwd_slabs', ((4, 2, 12, 12, 12, 128), (128,)), (4, 2, 1), 0): ((),),
+        ('norm_fwd_slabs', ((8, 2, 6, 6, 6, 256), (256,)), (8, 2, 1), 0): ((),),
+        ('pw16_fwd_norm', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 16, 1, 1, 1)), (2, 1, 2), 0): ((),),
+        ('up_dgrad', ((2, 12, 12, 12, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((2, 24, 24, 24, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((2, 48, 48, 48, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((2, 96, 96, 96, 16), (4096,)), (32,), 1): ((),),
+        ('up_fwd', ((2, 6, 6, 6, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((2, 12, 12, 12, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((2, 24, 24, 24, 64), (16384,), (32,)), (32,), 1): ((),),
     },
     "acdc": {
         ('norm_bwd', ((12, 1, 16, 16, 256), (12, 1, 16, 16, 256), (5, 2, 256)), (2, 2, 1), 0): ((),),
@@ -1083,6 +1810,25 @@ STEP_VARIANTS = {   # {workload: {norm key: epilogues the step uses}} (record_st
         ('norm_fwd', ((12, 1, 64, 64, 64), (64,), (64,)), (2, 2), 0): (('elem_mask', 'partial'), ('partial',), ('partial', 'out_slab')),
         ('norm_fwd', ((12, 1, 128, 128, 32), (32,), (32,)), (2, 2), 0): (('elem_mask', 'partial'), ('partial',), ('partial', 'out_slab')),
         ('norm_fwd', ((12, 1, 256, 256, 16), (16,), (16,)), (2, 2), 0): (('partial',), ('partial', 'out_slab')),
+        ('k2_wgrad', ((12, 1, 16, 16, 256), (12, 1, 16, 16, 128), (128, 256, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((12, 1, 32, 32, 128), (12, 1, 32, 32, 64), (64, 128, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((12, 1, 64, 64, 64), (12, 1, 64, 64, 32), (32, 64, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((12, 1, 128, 128, 32), (12, 1, 128, 128, 16), (16, 32, 1, 1)), (2,), 1): (('accumulate',),),
+        ('mix_box', ((6, 1, 256, 256, 1), (6, 1, 256, 256, 1)), (), 0): (('out',),),
+        ('norm_bwd_slabs', ((12, 1, 16, 16, 256), (4, 12, 1, 16, 16, 256), (5, 2, 256)), (4, 2, 2), 0): (('elem_mask', 'accumulate'),),
+        ('norm_fwd_slabs', ((4, 12, 1, 16, 16, 256), (256,), (256,)), (4, 2, 2), 0): ((), ('elem_mask',)),
+        ('conv3_c1_norm_bwd_wgrad', ((12, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 2, 2), 0): (('elem_mask', 'accumulate', 'dw_accumulate'),),
+        ('conv3_c1_norm_fwd', ((12, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 2, 2), 0): (('elem_mask',),),
+        ('mixloss_pair_bwd', ((12, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0): (('out', 'g_dev'),),
+        ('mixloss_pair_fwd', ((12, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0): ((),),
+        ('pw_fwd', ((12, 1, 16, 16, 128), (32768,)), (256,), 0): ((),),
+        ('pw_fwd', ((12, 1, 16, 16, 256), (32768,), (128,)), (128,), 1): ((),),
+        ('pw_fwd', ((12, 1, 32, 32, 64), (8192,)), (128,), 0): ((),),
+        ('pw_fwd', ((12, 1, 32, 32, 128), (8192,), (64,)), (64,), 1): ((),),
+        ('pw_fwd', ((12, 1, 64, 64, 32), (2048,)), (64,), 0): ((),),
+        ('pw_fwd', ((12, 1, 64, 64, 64), (2048,), (32,)), (32,), 1): ((),),
+        ('pw_fwd', ((12, 1, 128, 128, 16), (512,)), (32,), 0): ((),),
+        ('pw_fwd', ((12, 1, 128, 128, 32), (512,), (16,)), (16,), 1): ((),),
     },
 }
 
@@ -1092,8 +1838,11 @@ def variants_of(wl, key):
     return STEP_VARIANTS.get(wl, {}).get(key, ((),))
 
 
-def run_row(ops, dev, wl, key, g):
+def run_row(ops, dev, wl, key, g, table_key=None):
+    """one row through its driver; table_key: the STEP_KEYS row whose variants apply where `key` is its reduced twin"""
     fn = DRIVERS[key[0]]
     if key[0] in _VARIANT_OPS:
-        return fn(ops, dev, key, g, variants_of(wl, key))
+        return fn(ops, dev, key, g, variants_of(wl, table_key or key))
+    if fn is drive_pack_many:
+        return fn(ops, dev, key, g, wl)
     return fn(ops, dev, key, g)

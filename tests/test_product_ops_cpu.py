@@ -58,8 +58,8 @@ def _reduced_rows():
     seen, rows = set(), []
     for wl, k in P.driven_rows():
         rk = P.reduce_key(k)
-        if rk not in seen:
-            seen.add(rk)
+        if (rk, wl if k[0].endswith("pack_many") else None) not in seen:        # (a pack row is its workload's network, whatever the key)
+            seen.add((rk, wl if k[0].endswith("pack_many") else None))
             rows.append((wl, k, rk))
     return rows
 
@@ -73,8 +73,195 @@ def _reduced_rows():
                          ids=[P.row_id(r[0], r[1]) for r in _reduced_rows()])
 def test_product_op_reduced_on_simulator(emu_ops, wl, key, rkey):  # noqa: F811
     g = torch.Generator().manual_seed(5)
-    fn = P.DRIVERS[rkey[0]]
-    if rkey[0] in P._VARIANT_OPS:
-        fn(emu_ops, torch.device("cpu"), rkey, g, P.variants_of(wl, key))
-    else:
-        fn(emu_ops, torch.device("cpu"), rkey, g)
+    P.run_row(emu_ops, torch.device("cpu"), wl, rkey, g, table_key=key)
+
+
+# -------------------------------------------------------------------------------------------------- the new references' own tests
+
+
+def test_k2_references_match_torch():
+    """down64 / up64 / k2_wgrad64 against torch's fp64 conv3d(stride=2), conv_transpose3d and torch.nn.grad weight gradients"""
+    F = torch.nn.functional
+    g = torch.Generator().manual_seed(13)
+    cf = lambda t: t.permute(0, 4, 1, 2, 3)          # noqa: E731  (channels-last -> NCDHW view)
+    cl = lambda t: t.permute(0, 2, 3, 4, 1)          # noqa: E731
+    x = torch.randn(2, 4, 6, 10, 3, generator=g, dtype=torch.float64)
+    w = torch.randn(5, 3, 2, 2, 2, generator=g, dtype=torch.float64)
+    y = cl(F.conv3d(cf(x), w, stride=2))
+    assert torch.allclose(P.down64(x, w), y, rtol=1e-12, atol=1e-12)
+    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    assert torch.allclose(P.up64(dy, w), cl(F.conv_transpose3d(cf(dy), w, stride=2)), rtol=1e-12, atol=1e-12)       # = the down conv's dgrad
+    gw = torch.nn.grad.conv3d_weight(cf(x), w.shape, cf(dy), stride=2)
+    assert torch.allclose(P.k2_wgrad64(x, dy, 0), gw, rtol=1e-12, atol=1e-12)
+    # transposed conv: coarse xt [.., 5] -> fine [.., 3] with the weight [5, 3, 2, 2, 2]; its weight gradient is the twin conv's
+    xt = torch.randn(2, 2, 3, 5, 5, generator=g, dtype=torch.float64)
+    yt = cl(F.conv_transpose3d(cf(xt), w, stride=2))
+    assert torch.allclose(P.up64(xt, w), yt, rtol=1e-12, atol=1e-12)
+    dyt = torch.randn(yt.shape, generator=g, dtype=torch.float64)
+    assert torch.allclose(P.down64(dyt, w), cl(F.conv3d(cf(dyt), w, stride=2)), rtol=1e-12, atol=1e-12)             # = the transposed conv's dgrad
+    gwt = torch.nn.grad.conv3d_weight(cf(dyt), w.shape, cf(xt), stride=2)
+    assert torch.allclose(P.k2_wgrad64(xt, dyt, 1), gwt, rtol=1e-12, atol=1e-12)
+    # 1x1 conv on a D == 1 tensor
+    x2 = torch.randn(3, 1, 4, 5, 6, generator=g, dtype=torch.float64)
+    dy2 = torch.randn(3, 1, 4, 5, 7, generator=g, dtype=torch.float64)
+    gw2 = torch.nn.grad.conv2d_weight(x2[:, 0].permute(0, 3, 1, 2), (7, 6, 1, 1), dy2[:, 0].permute(0, 3, 1, 2))
+    assert torch.allclose(P.k2_wgrad64(x2, dy2, 2), gw2, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("flavour,ls", [(0, (4, 6, 8, 8, 2)), (1, (4, 1, 12, 12, 4))], ids=["la", "acdc"])
+def test_mixloss_closed_form_matches_oracle_autograd(flavour, ls):
+    """mixloss_pair64 (terms, total and d total / d logits in closed form) against fp64 autograd of the oracle's mix_loss_la /
+    mix_loss_acdc, for both boxes of the drivers: <= 1e-12; and its cond bounds its gradient"""
+    import bcp_oracle as O
+    g = torch.Generator().manual_seed(3)
+    sp, C = ls[1:4], ls[-1]
+    N = ls[0] // 2
+    w = ((1.0, 0.5), (0.5, 1.0))
+    for box6 in P._boxes(sp, g):
+        logits, labs = P._loss_inputs(g, ls, C)
+        o, t, gr, cond = P.mixloss_pair64(logits, labs, box6, flavour, w)
+        L = logits.double().requires_grad_(True)
+        nc = L.permute(0, 4, 1, 2, 3)
+        mask = (~P._in_box(sp, box6)).double().unsqueeze(0).expand(N, *sp)
+        terms = []
+        for h in range(2):
+            xh = nc[h * N:(h + 1) * N]
+            if flavour == 0:
+                terms.append(O.mix_loss_la(xh, labs[h][0], labs[h][1], mask, l_weight=w[h][0], u_weight=w[h][1]))
+            else:
+                terms.append(O.mix_loss_acdc(xh[:, :, 0], labs[h][0][:, 0], labs[h][1][:, 0], mask[:, 0], l_weight=w[h][0], u_weight=w[h][1]))
+        if flavour == 0:
+            tot = terms[0] + terms[1]
+            d = max(abs(float(terms[h].detach()) - float(o[h, 0])) for h in range(2))
+        else:
+            tot = ((terms[1][0] + terms[0][0]) + (terms[1][1] + terms[0][1])) / 2
+            d = max(abs(float(terms[h][j].detach()) - float(o[h, j])) for h in range(2) for j in range(2))
+        tot.backward()
+        assert d <= 1e-12 and abs(float(tot.detach()) - float(t)) <= 1e-12, (box6, d)
+        assert float((L.grad - gr).abs().max()) <= 1e-12 and P.elementwise_ratio(L.grad, gr, cond)[0] <= 1e-12, box6
+        assert bool((cond >= gr.abs() * (1 - 1e-12)).all())
+
+
+def test_every_step_op_has_a_driver():
+    """a new op in a step cannot go undriven: every op of STEP_KEYS has a driver, and the driven rows are the whole table plus the
+    keys only a statistics-only norm call uses"""
+    assert {k[0] for _, k in P.table_rows()} <= set(P.DRIVERS)
+    rows = P.driven_rows()
+    assert len(P.table_rows()) == 223 and set(P.table_rows()) <= set(rows)
+    extra = [k for _, k in rows if (_, k) not in set(P.table_rows())]
+    assert all(k[0] == "norm_fwd" for k in extra), extra
+
+
+# -------------------------------------------------------------------------------------------------- would the drivers notice?
+
+
+class _Corrupt:
+    """the simulator's ops with one op replaced by fn(orig, *args, **kw): a driver run on it must raise.  `pairs` keeps (clean, corrupted)
+    results for the note on what a max-scaled close() or a rel-L2 1e-4 test would have said"""
+
+    def __init__(self, ops, name, fn):
+        self._ops, self._name, self._fn, self.pairs = ops, name, fn, []
+
+    def __getattr__(self, n):
+        v = getattr(self._ops, n)
+        if n != self._name:
+            return v
+        return lambda *a, **k: self._fn(self, v, *a, **k)
+
+
+def _first(r):
+    return r if isinstance(r, torch.Tensor) else r[0]
+
+
+def _scaled(sel, factor):
+    """corruption: the op's (first) result with the elements sel(result) selects scaled by `factor` (0: zeroed)"""
+    def fn(c, orig, *a, **k):
+        r = orig(*a, **k)
+        t = _first(r)
+        clean = t.clone()
+        sel(t).mul_(factor)
+        c.pairs.append((clean, t.clone()))
+        return r
+    return fn
+
+
+def _rerun(change):
+    """corruption: the op run on changed arguments (change(args) -> args)"""
+    def fn(c, orig, *a, **k):
+        clean = _first(orig(*a, **k)).clone()
+        r = orig(*change(list(a)), **k)
+        c.pairs.append((clean, _first(r).clone()))
+        return r
+    return fn
+
+
+def _drop_last_slab(i):
+    def change(a):
+        a[i] = torch.cat([a[i][:-1], torch.zeros_like(a[i][-1:])])
+        return a
+    return change
+
+
+def _shift_box(a):
+    b = list(a[2])
+    b[2] += 1                                        # the box's w origin: two faces move by one voxel
+    a[2] = tuple(b)
+    return a
+
+
+def _ragged_tail(t):
+    rows = t.reshape(-1, t.shape[-1])
+    return rows[(rows.shape[0] - 1) // 64 * 64:]
+
+
+def _la_row(op, pick=0):
+    return [(wl, k) for wl, k in P.table_rows() if wl == "la" and k[0] == op][pick]
+
+
+# case: (op of the LA row driven, op corrupted, corruption[, which of the op's LA rows]).  What the older comparators say of the same
+# outputs at these reduced shapes (the test prints it): kernel_checks.close(), scaled by the tensor's largest element, accepts only the
+# conv pack's changed word; a rel-L2 1e-4 test accepts the scaled first-layer channel (9.6e-5) and both pack words, and is within 4x of
+# accepting every 1 + 2^-10 / 2^-12 scaling (1.2e-4 .. 6.7e-4).
+SENSITIVITY = {
+    "up-subposition": ("up_fwd", "up_fwd", _scaled(lambda t: t[:, 1::2, 0::2, 1::2], 1 + 2.0 ** -10), -1),
+    "down-ragged-block": ("down_fwd", "down_fwd", _scaled(_ragged_tail, 0.0), -1),             # (2 x 7 x 7 x 5 = 490 rows: 7 blocks of 64 + 42)
+    "wgrad-subposition": ("k2_wgrad", "k2_wgrad", _scaled(lambda t: t[:, :, 1, 0, 1], 1 + 2.0 ** -10)),
+    "fwd-slab-dropped": ("norm_fwd_slabs", "norm_fwd_slabs", _rerun(_drop_last_slab(0))),
+    "bwd-slab-dropped": ("norm_bwd_slabs", "norm_bwd_slabs", _rerun(_drop_last_slab(1))),
+    "loss-class-gradient": ("mixloss_pair_bwd", "mixloss_pair_bwd", _scaled(lambda t: t[..., 1], 1 + 2.0 ** -12)),
+    "box-face-shifted": ("mix_box", "mix_box", _rerun(_shift_box)),
+    "c1-activation-channel": ("conv3_c1_norm_fwd", "conv3_c1_norm_fwd", _scaled(lambda t: t[..., 5], 1 + 2.0 ** -10)),
+    # (the weight gradient's bound carries the log2(n) allowance for the norm backward's two means over every voxel: a 2^-10 scaling of a
+    #  tap is inside it, a dropped tap -- a tap loop one short -- is not)
+    "c1-wgrad-tap": ("conv3_c1_norm_bwd_wgrad", "conv3_c1_norm_bwd_wgrad", _scaled(lambda t: t[:, :, 0, 1, 2], 0.0)),
+    "head-logit-class": ("pw16_fwd_norm", "pw16_fwd_norm", _scaled(lambda t: t[..., 1], 1 + 2.0 ** -10)),
+    "head-gradient-channel": ("pw16_bwd_norm_bwd", "pw16_bwd_norm_bwd", _scaled(lambda t: t[..., 3], 1 + 2.0 ** -10)),
+    "pack-one-word": ("conv3_pack_many", "conv3_pack", _scaled(lambda t: t[7:8], 1 + 2.0 ** -10)),
+    "k2-pack-one-word": ("k2_pack_many", "k2_pack", _scaled(lambda t: t[7:8], 1 + 2.0 ** -10)),
+}
+
+
+@pytest.mark.parametrize("case", sorted(SENSITIVITY))
+def test_driver_rejects_corruption(emu_ops, case):  # noqa: F811
+    """each new driver, on the simulator at the reduced LA shape, with its op corrupted the way a real bug would: one (a, b, c)
+    sub-position of a transposed conv scaled by 1 + 2^-10, the last ragged 64-row block of a down conv zeroed, one slab dropped from a
+    slab sum, one class's loss gradient scaled by 1 + 2^-12, one box face shifted by a voxel, ... -- the driver must raise.  The printed
+    note says whether kernel_checks.close() (max-scaled) or a rel-L2 1e-4 test would have accepted the same output."""
+    import kernel_checks as K
+    row_op, bad_op, fn, *pick = SENSITIVITY[case]
+    wl, key = _la_row(row_op, *pick)
+    rkey = P.reduce_key(key)
+    g = torch.Generator().manual_seed(5)
+    P.run_row(emu_ops, torch.device("cpu"), wl, rkey, g, table_key=key)                  # the clean op passes
+    bad = _Corrupt(emu_ops, bad_op, fn)
+    with pytest.raises(AssertionError):
+        P.run_row(bad, torch.device("cpu"), wl, rkey, torch.Generator().manual_seed(5), table_key=key)
+    assert bad.pairs, "the corrupted op was not called"
+    clean, corrupt = bad.pairs[0]
+    try:
+        K.close(corrupt, clean)
+        closes = True
+    except AssertionError:
+        closes = False
+    print(f"[sensitivity] {case}: close() {'accepts' if closes else 'rejects'} it, rel-L2 {P.rel_l2(corrupt, clean):.2e} "
+          f"({'accepted' if P.rel_l2(corrupt, clean) < 1e-4 else 'rejected'} at 1e-4)")
