@@ -14,6 +14,12 @@ autograd, mix_box and the largest-component filter bit for bit, the networks' ba
 packs, the optimisers.  Rows stay at the in-step shapes because the route is a function of the shape (csrc/gemm.hip: pick_nt, stat_plan,
 tn_groups; split-K slab counts; fused statistics): each driver asserts on the device that the in-step route was taken.
 
+Beside the three self-training steps the table holds the other phases the drivers run: one pre-training step per driver (la_pre,
+pancreas_pre, acdc_pre: the labeled half of the batch, one norm group, the single mix loss with the all-zero box), one validation pass
+per driver (la_val, pancreas_val, acdc_val: eval-mode networks on a full chunk and a remainder chunk of one, operands without |max|,
+norm_eval, the sliding-window accumulation, the overlap counts) and the LA step at the driver's default batch 8 (la8).  A key that
+already stands under an earlier workload with the same flags is driven once.
+
 The comparator: every element is held to |out - ref64| <= tau * cond, where cond is the same linear op applied in fp64 to |x| and |w| (a
 per-element bound on what rounding can do).  A rel-L2 test spreads an error confined to one tile over the whole tensor; this one does not.
 """
@@ -174,12 +180,22 @@ def k2_wgrad64(x, dy, kind):
 # -------------------------------------------------------------------------------------------------- the steps' keys
 
 
+VAL_CASES = {"la_val": (112, 112, 96), "pancreas_val": (96, 96, 112), "acdc_val": (17, 256, 256)}
+
+
 def make_step(workload, dev):
-    """one workload's step as bench.py builds it (configs[1] LA batch 4 / 2 labeled, ACDC 24 / 12, pancreas 4 x 96^3)"""
+    """one workload's step as bench.py builds it (configs[1] LA batch 4 / 2 labeled, ACDC 24 / 12, pancreas 4 x 96^3; la8: the LA
+    driver's default batch 8 / 4 labeled), the pre-training step of the same driver on the labeled half of that batch (*_pre), or one
+    validation pass through the function the driver calls (*_val) on a synthetic case of VAL_CASES' extents: one full chunk of patches
+    (slices) and a remainder chunk of one"""
     from bcp_amd import synth, train_step
     seed = 1337
     np.random.seed(seed)
-    if workload == "la":
+    base, _, phase = workload.partition("_")
+    if workload == "la8":
+        base, phase = "la", "8"
+    ema_model = None
+    if base == "la":
         from bcp_amd.networks.net_factory import net_factory
         torch.manual_seed(seed)
         model = net_factory(net_type="VNet", in_chns=1, class_num=2, mode="train")
@@ -189,48 +205,90 @@ def make_step(workload, dev):
         ema_model.load_state_dict(model.state_dict())
         model.train(); ema_model.train()
         opt = train_step.FlatSGD(model, lr=0.01, momentum=0.9, weight_decay=1e-4)
-        vol, lab = synth.la_batch(4, seed=seed)
-        vol, lab = vol.to(dev), lab.to(dev)
+        if phase == "val":
+            from bcp_amd.utils import test_3d_patch as T3
+            vol, lab = synth.la_batch(1, shape=VAL_CASES[workload], seed=seed)
+            case = [(vol[0, 0].to(dev), lab[0].to(dev))]
 
-        def step():
-            return train_step.la_self_train_step(model, ema_model, opt, vol, lab, 2)
-    elif workload == "acdc":
+            def step():
+                return T3.var_all_case_LA(model, 2, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, cases=case)
+        else:
+            batch = 8 if phase == "8" else 4
+            vol, lab = synth.la_batch(batch, seed=seed)
+            vol, lab = vol.to(dev), lab.to(dev)
+            if phase == "pre":
+                def step():
+                    return train_step.la_pre_train_step(model, opt, vol[:batch // 2], lab[:batch // 2])
+            else:
+                def step():
+                    return train_step.la_self_train_step(model, ema_model, opt, vol, lab, batch // 2)
+    elif base == "acdc":
         from bcp_amd.networks.net_factory import BCP_net
         torch.manual_seed(seed)
         model, ema_model = BCP_net(in_chns=1, class_num=4), BCP_net(in_chns=1, class_num=4, ema=True)
         ema_model.load_state_dict(model.state_dict())
         model.train(); ema_model.train()
         opt = train_step.FlatSGD(model, lr=0.01, momentum=0.9, weight_decay=1e-4)
-        vol, lab = synth.acdc_batch(24, seed=seed)
-        vol, lab = vol.to(dev), lab.to(dev)
+        if phase == "val":
+            from bcp_amd.utils import val_2d
+            vol, lab = synth.acdc_batch(VAL_CASES[workload][0], seed=seed)
+            image, label = vol[:, 0].unsqueeze(0).to(dev), lab.reshape(1, -1, 256, 256).to(dev)
 
-        def step():
-            return train_step.acdc_self_train_step(model, ema_model, opt, vol, lab, 12)
-    elif workload == "pancreas":
+            def step():
+                return val_2d.test_single_volume(image, label, model, classes=4)
+        else:
+            vol, lab = synth.acdc_batch(24, seed=seed)
+            vol, lab = vol.to(dev), lab.to(dev)
+            if phase == "pre":
+                def step():
+                    return train_step.acdc_pre_train_step(model, opt, vol[:12], lab[:12])
+            else:
+                def step():
+                    return train_step.acdc_self_train_step(model, ema_model, opt, vol, lab, 12)
+    elif base == "pancreas":
         from bcp_amd.pancreas import train_pancreas as TP
         from bcp_amd.pancreas.Vnet import create_Vnet
         torch.manual_seed(seed)
         model, ema_model = create_Vnet(), create_Vnet(ema=True)
         ema_model.load_state_dict(model.state_dict())
         opt = train_step.FlatAdam(model, lr=1e-3)
-        streams = TP._streams(dev, 4, 1, seed=seed)
+        if phase == "val":
+            from bcp_amd.pancreas.test_util import test_calculate_metric
+            vol, lab = synth.la_batch(1, shape=VAL_CASES[workload], seed=seed)
+            case = [(vol[0, 0].to(dev), lab[0].to(dev))]
+            stride = (18, 4)                   # (train_pancreas.py's --val_stride default)
 
-        def step():
-            return TP.ema_cutmix(model, ema_model, opt, streams, 1)
+            def step():
+                return test_calculate_metric(model, case, num_classes=2, dim=(96, 96, 96), s_xy=stride[0], s_z=stride[1])
+        else:
+            streams = TP._streams(dev, 4, 1, seed=seed)
+            if phase == "pre":
+                def step():
+                    return TP.pretrain(model, opt, streams, 1)
+            else:
+                def step():
+                    return TP.ema_cutmix(model, ema_model, opt, streams, 1)
     else:
         raise ValueError(workload)
     model.volatile_io = ema_model.volatile_io = True
     return step
 
 
+def setup_steps(workload):
+    """steps before the profiled one: a training pass is replayed from a plan (the first step records it, the second captures it); a
+    validation pass runs eagerly -- eval() takes no plan"""
+    return 0 if workload.endswith("_val") else 2
+
+
 def record_step_keys(workload, steps=1):
     """the set of (op, shapes, ints, namax) keys one replayed step of `workload` records under the profile hooks (two set-up steps first:
-    the first records the launch plans, the second captures them -- the timed steps of bench.py are replays)"""
+    the first records the launch plans, the second captures them -- the timed steps of bench.py are replays; a validation pass is
+    eager and needs none)"""
     from bcp_amd import plan
     from bcp_amd.hip_ops import Ops
     dev = torch.device("cuda:0")
     step = make_step(workload, dev)
-    for _ in range(2):
+    for _ in range(setup_steps(workload)):
         step()
     torch.cuda.synchronize()
     ops = Ops.product()
@@ -248,7 +306,7 @@ def record_step_keys(workload, steps=1):
 
 # -------------------------------------------------------------------------------------------------- the table
 # Every key one replayed step of each product workload records (LA configs[1]: batch 4, two labeled, networks grouped 2; pancreas 4 x 96^3;
-# ACDC 24 slices of 256 x 256 in groups of 12).  A new shape or dispatch route changes the set: test_step_keys_in_table then fails until
+# ACDC 24 slices of 256 x 256 in groups of 12), then the pre-training steps, the validation passes and the LA batch-8 step (make_step).  A new shape or dispatch route changes the set: test_step_keys_in_table then fails until
 # the key is added here (and, where its family has a driver below, checked).
 STEP_KEYS = {
     "la": (
@@ -480,14 +538,495 @@ STEP_KEYS = {
         ('pw_fwd', ((12, 1, 128, 128, 32), (512,), (16,)), (16,), 1),
         ('sgd', ((1813764,), (1813764,), (1813764,)), (), 0),
     ),
+    "la_pre": (
+        ('conv3_c1_norm_bwd_wgrad', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0),
+        ('conv3_c1_norm_fwd', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0),
+        ('conv3_dgrad_bwdstats', ((1, 56, 56, 40, 32), (99360,), (1, 56, 56, 40, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((1, 112, 112, 80, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd', ((1, 28, 28, 20, 64), (397344,)), (64, 3), 1),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd_raw', ((1, 14, 14, 10, 128), (1589280,)), (128, 3, 4), 1),
+        ('conv3_fwd_stats', ((1, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 1), 1),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_wgrad', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((1, 14, 14, 10, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((1, 28, 28, 20, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((1, 56, 56, 40, 32), (4096,)), (16,), 1),
+        ('down_dgrad', ((1, 7, 7, 5, 256), (262144,)), (128,), 1),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_wgrad', ((1, 112, 112, 80, 16), (1, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 7, 7, 5, 256), (1, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0),
+        ('mixloss_bwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('mixloss_fwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('norm_bwd', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (5, 1, 16)), (1, 1, True), 0),
+        ('norm_bwd', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (5, 1, 128)), (1, 1, True), 0),
+        ('norm_bwd', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (5, 1, 64)), (1, 1, True), 0),
+        ('norm_bwd', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (5, 1, 32)), (1, 1, True), 0),
+        ('norm_bwd', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (5, 1, 256)), (1, 1, True), 0),
+        ('norm_bwd_slabs', ((1, 14, 14, 10, 128), (4, 1, 14, 14, 10, 128), (5, 1, 128)), (4, 1, 1), 0),
+        ('norm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1, 1), 0),
+        ('norm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1, 1), 0),
+        ('norm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1, 1), 0),
+        ('norm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1, 1), 0),
+        ('norm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1, 1), 0),
+        ('norm_fwd_slabs', ((4, 1, 14, 14, 10, 128), (128,), (128,)), (4, 1, 1), 0),
+        ('pw16_bwd_norm_bwd', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1), 0),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1, 2), 0),
+        ('sgd', ((9448868,), (9448868,), (9448868,)), (), 0),
+        ('up_dgrad', ((1, 112, 112, 80, 16), (4096,)), (32,), 1),
+        ('up_dgrad', ((1, 14, 14, 10, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((1, 28, 28, 20, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((1, 56, 56, 40, 32), (16384,)), (64,), 1),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+    ),
+    "pancreas_pre": (
+        ('adam', ((9443268,), (9443268,), (9443268,)), (3,), 0),
+        ('conv3_c1_norm_bwd_wgrad', ((1, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0),
+        ('conv3_c1_norm_fwd', ((1, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0),
+        ('conv3_dgrad_bwdstats', ((1, 48, 48, 48, 32), (99360,), (1, 48, 48, 48, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((1, 24, 24, 24, 64), (397344,)), (64, 3), 1),
+        ('conv3_fwd', ((1, 24, 24, 24, 64), (397344,), (64,)), (64, 3), 1),
+        ('conv3_fwd', ((1, 6, 6, 6, 256), (6357024,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 6, 6, 6, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 96, 96, 96, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd_raw', ((1, 12, 12, 12, 128), (1589280,)), (128, 3, 4), 1),
+        ('conv3_fwd_stats', ((1, 48, 48, 48, 32), (99360,), (32,)), (32, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 96, 96, 96, 16), (24864,), (16,)), (16, 3, 1), 1),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_wgrad', ((1, 12, 12, 12, 128), (1, 12, 12, 12, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 24, 24, 24, 64), (1, 24, 24, 24, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 48, 48, 48, 32), (1, 48, 48, 48, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 6, 6, 6, 256), (1, 6, 6, 6, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 96, 96, 96, 16), (1, 96, 96, 96, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((1, 12, 12, 12, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((1, 24, 24, 24, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((1, 48, 48, 48, 32), (4096,)), (16,), 1),
+        ('down_dgrad', ((1, 6, 6, 6, 256), (262144,)), (128,), 1),
+        ('down_fwd', ((1, 12, 12, 12, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((1, 24, 24, 24, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((1, 48, 48, 48, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((1, 96, 96, 96, 16), (4096,), (32,)), (32,), 1),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_wgrad', ((1, 12, 12, 12, 128), (1, 24, 24, 24, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 12, 12, 12, 128), (1, 6, 6, 6, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 24, 24, 24, 64), (1, 12, 12, 12, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 24, 24, 24, 64), (1, 48, 48, 48, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 48, 48, 48, 32), (1, 24, 24, 24, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 48, 48, 48, 32), (1, 96, 96, 96, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 6, 6, 6, 256), (1, 12, 12, 12, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 96, 96, 96, 16), (1, 48, 48, 48, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('mix_box', ((1, 96, 96, 96, 1), (1, 96, 96, 96, 1)), (), 0),
+        ('mixloss_bwd', ((1, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0),
+        ('mixloss_fwd', ((1, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0),
+        ('norm_bwd', ((1, 12, 12, 12, 128), (1, 12, 12, 12, 128), (5, 1, 128)), (1, 1, False), 0),
+        ('norm_bwd', ((1, 24, 24, 24, 64), (1, 24, 24, 24, 64), (5, 1, 64)), (1, 1, False), 0),
+        ('norm_bwd', ((1, 48, 48, 48, 32), (1, 48, 48, 48, 32), (5, 1, 32)), (1, 1, False), 0),
+        ('norm_bwd', ((1, 6, 6, 6, 256), (1, 6, 6, 6, 256), (5, 1, 256)), (1, 1, False), 0),
+        ('norm_bwd', ((1, 96, 96, 96, 16), (1, 96, 96, 96, 16), (5, 1, 16)), (1, 1, False), 0),
+        ('norm_bwd_slabs', ((1, 12, 12, 12, 128), (4, 1, 12, 12, 12, 128), (5, 1, 128)), (4, 1, 1), 0),
+        ('norm_fwd', ((1, 12, 12, 12, 128),), (1, 1), 0),
+        ('norm_fwd', ((1, 24, 24, 24, 64),), (1, 1), 0),
+        ('norm_fwd', ((1, 48, 48, 48, 32),), (1, 1), 0),
+        ('norm_fwd', ((1, 6, 6, 6, 256),), (1, 1), 0),
+        ('norm_fwd', ((1, 96, 96, 96, 16),), (1, 1), 0),
+        ('norm_fwd_slabs', ((4, 1, 12, 12, 12, 128), (128,)), (4, 1, 1), 0),
+        ('pw16_bwd_norm_bwd', ((1, 96, 96, 96, 16), (5, 1, 16), (1, 96, 96, 96, 2)), (1, 1), 0),
+        ('pw16_fwd_norm', ((1, 96, 96, 96, 16), (5, 1, 16), (2, 16, 1, 1, 1)), (1, 1, 2), 0),
+        ('up_dgrad', ((1, 12, 12, 12, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((1, 24, 24, 24, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((1, 48, 48, 48, 32), (16384,)), (64,), 1),
+        ('up_dgrad', ((1, 96, 96, 96, 16), (4096,)), (32,), 1),
+        ('up_fwd', ((1, 12, 12, 12, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((1, 24, 24, 24, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((1, 48, 48, 48, 32), (4096,), (16,)), (16,), 1),
+        ('up_fwd', ((1, 6, 6, 6, 256), (262144,), (128,)), (128,), 1),
+    ),
+    "acdc_pre": (
+        ('bilinear2x_bwd', ((6, 1, 128, 128, 64),), (32, 32), 0),
+        ('bilinear2x_bwd', ((6, 1, 256, 256, 32),), (16, 16), 0),
+        ('bilinear2x_bwd', ((6, 1, 32, 32, 256),), (128, 128), 0),
+        ('bilinear2x_bwd', ((6, 1, 64, 64, 128),), (64, 64), 0),
+        ('bilinear2x_fwd', ((6, 1, 128, 128, 16), (6, 1, 256, 256, 32)), (16,), 1),
+        ('bilinear2x_fwd', ((6, 1, 16, 16, 128), (6, 1, 32, 32, 256)), (128,), 1),
+        ('bilinear2x_fwd', ((6, 1, 32, 32, 64), (6, 1, 64, 64, 128)), (64,), 1),
+        ('bilinear2x_fwd', ((6, 1, 64, 64, 32), (6, 1, 128, 128, 64)), (32,), 1),
+        ('conv3_c1_norm_bwd_wgrad', ((6, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 1, 2), 0),
+        ('conv3_c1_norm_fwd', ((6, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 1, 2), 0),
+        ('conv3_dgrad_bwdstats', ((6, 1, 128, 128, 32), (34848,), (6, 1, 128, 128, 32)), (32, 1, 2), 1),
+        ('conv3_fwd', ((6, 1, 128, 128, 32), (17440,)), (16, 1), 1),
+        ('conv3_fwd', ((6, 1, 128, 128, 32), (34848,)), (32, 1), 1),
+        ('conv3_fwd', ((6, 1, 128, 128, 32), (69664,)), (64, 1), 1),
+        ('conv3_fwd', ((6, 1, 16, 16, 256), (1114144,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 256, 256, 16), (17440,)), (32, 1), 1),
+        ('conv3_fwd', ((6, 1, 256, 256, 16), (8736,)), (16, 1), 1),
+        ('conv3_fwd', ((6, 1, 256, 256, 16), (8736,), (4,)), (4, 1), 1),
+        ('conv3_fwd', ((6, 1, 256, 256, 4), (8736,)), (16, 1), 0),
+        ('conv3_fwd', ((6, 1, 32, 32, 128), (1114144,)), (256, 1), 1),
+        ('conv3_fwd', ((6, 1, 32, 32, 128), (278560,)), (64, 1), 1),
+        ('conv3_fwd', ((6, 1, 32, 32, 128), (557088,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 32, 32, 128), (557088,), (128,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 32, 32, 256), (1114144,), (128,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 32, 32, 64), (278560,), (128,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 64, 64, 64), (139296,)), (64, 1), 1),
+        ('conv3_fwd', ((6, 1, 64, 64, 64), (278560,)), (128, 1), 1),
+        ('conv3_fwd', ((6, 1, 64, 64, 64), (69664,)), (32, 1), 1),
+        ('conv3_fwd_raw', ((6, 1, 16, 16, 128), (1114144,)), (256, 1, 4), 1),
+        ('conv3_fwd_raw', ((6, 1, 16, 16, 256), (2228256,)), (256, 1, 4), 1),
+        ('conv3_fwd_stats', ((6, 1, 128, 128, 16), (17440,), (32,)), (32, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 128, 128, 32), (34848,), (32,)), (32, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 128, 128, 64), (69664,), (32,)), (32, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 256, 256, 16), (8736,), (16,)), (16, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 256, 256, 32), (17440,), (16,)), (16, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 64, 64, 128), (278560,), (64,)), (64, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 64, 64, 32), (69664,), (64,)), (64, 1, 1), 1),
+        ('conv3_fwd_stats', ((6, 1, 64, 64, 64), (139296,), (64,)), (64, 1, 1), 1),
+        ('conv3_pack_many', ((1440,),), (36,), 0),
+        ('conv3_wgrad', ((6, 1, 128, 128, 16), (6, 1, 128, 128, 32), (32, 16, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 128, 128, 32), (6, 1, 128, 128, 32), (32, 32, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 128, 128, 64), (6, 1, 128, 128, 32), (32, 64, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 16, 16, 128), (6, 1, 16, 16, 256), (256, 128, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 16, 16, 256), (6, 1, 16, 16, 256), (256, 256, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 256, 256, 16), (6, 1, 256, 256, 16), (16, 16, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 256, 256, 16), (6, 1, 256, 256, 4), (4, 16, 3, 3)), (1,), 1),
+        ('conv3_wgrad', ((6, 1, 256, 256, 32), (6, 1, 256, 256, 16), (16, 32, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 32, 32, 128), (6, 1, 32, 32, 128), (128, 128, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 32, 32, 256), (6, 1, 32, 32, 128), (128, 256, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 32, 32, 64), (6, 1, 32, 32, 128), (128, 64, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 64, 64, 128), (6, 1, 64, 64, 64), (64, 128, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 64, 64, 32), (6, 1, 64, 64, 64), (64, 32, 3, 3)), (1,), 2),
+        ('conv3_wgrad', ((6, 1, 64, 64, 64), (6, 1, 64, 64, 64), (64, 64, 3, 3)), (1,), 2),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('k2_wgrad', ((6, 1, 128, 128, 32), (6, 1, 128, 128, 16), (16, 32, 1, 1)), (2,), 1),
+        ('k2_wgrad', ((6, 1, 16, 16, 256), (6, 1, 16, 16, 128), (128, 256, 1, 1)), (2,), 1),
+        ('k2_wgrad', ((6, 1, 32, 32, 128), (6, 1, 32, 32, 64), (64, 128, 1, 1)), (2,), 1),
+        ('k2_wgrad', ((6, 1, 64, 64, 64), (6, 1, 64, 64, 32), (32, 64, 1, 1)), (2,), 1),
+        ('maxpool2d_bwd', ((6, 1, 128, 128, 32), (6, 1, 64, 64, 32), (6, 1, 128, 128, 32)), (), 1),
+        ('maxpool2d_bwd', ((6, 1, 256, 256, 16), (6, 1, 128, 128, 16), (6, 1, 256, 256, 16)), (), 1),
+        ('maxpool2d_bwd', ((6, 1, 32, 32, 128), (6, 1, 16, 16, 128), (6, 1, 32, 32, 128)), (), 1),
+        ('maxpool2d_bwd', ((6, 1, 64, 64, 64), (6, 1, 32, 32, 64), (6, 1, 64, 64, 64)), (), 1),
+        ('maxpool2d_fwd', ((6, 1, 128, 128, 32),), (), 1),
+        ('maxpool2d_fwd', ((6, 1, 256, 256, 16),), (), 1),
+        ('maxpool2d_fwd', ((6, 1, 32, 32, 128),), (), 1),
+        ('maxpool2d_fwd', ((6, 1, 64, 64, 64),), (), 1),
+        ('mix_box', ((6, 1, 256, 256, 1), (6, 1, 256, 256, 1)), (), 0),
+        ('mixloss_bwd', ((6, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0),
+        ('mixloss_fwd', ((6, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0),
+        ('norm_bwd', ((6, 1, 128, 128, 32), (6, 1, 128, 128, 32), (5, 1, 32)), (1, 2, True), 0),
+        ('norm_bwd', ((6, 1, 16, 16, 256), (6, 1, 16, 16, 256), (5, 1, 256)), (1, 2, True), 0),
+        ('norm_bwd', ((6, 1, 256, 256, 16), (6, 1, 256, 256, 16), (5, 1, 16)), (1, 2, True), 0),
+        ('norm_bwd', ((6, 1, 32, 32, 128), (6, 1, 32, 32, 128), (5, 1, 128)), (1, 2, True), 0),
+        ('norm_bwd', ((6, 1, 64, 64, 64), (6, 1, 64, 64, 64), (5, 1, 64)), (1, 2, True), 0),
+        ('norm_bwd_slabs', ((6, 1, 16, 16, 256), (4, 6, 1, 16, 16, 256), (5, 1, 256)), (4, 1, 2), 0),
+        ('norm_fwd', ((6, 1, 128, 128, 32), (32,), (32,)), (1, 2), 0),
+        ('norm_fwd', ((6, 1, 256, 256, 16), (16,), (16,)), (1, 2), 0),
+        ('norm_fwd', ((6, 1, 32, 32, 128), (128,), (128,)), (1, 2), 0),
+        ('norm_fwd', ((6, 1, 64, 64, 64), (64,), (64,)), (1, 2), 0),
+        ('norm_fwd_slabs', ((4, 6, 1, 16, 16, 256), (256,), (256,)), (4, 1, 2), 0),
+        ('pw_fwd', ((6, 1, 128, 128, 16), (512,)), (32,), 0),
+        ('pw_fwd', ((6, 1, 128, 128, 32), (512,), (16,)), (16,), 1),
+        ('pw_fwd', ((6, 1, 16, 16, 128), (32768,)), (256,), 0),
+        ('pw_fwd', ((6, 1, 16, 16, 256), (32768,), (128,)), (128,), 1),
+        ('pw_fwd', ((6, 1, 32, 32, 128), (8192,), (64,)), (64,), 1),
+        ('pw_fwd', ((6, 1, 32, 32, 64), (8192,)), (128,), 0),
+        ('pw_fwd', ((6, 1, 64, 64, 32), (2048,)), (64,), 0),
+        ('pw_fwd', ((6, 1, 64, 64, 64), (2048,), (32,)), (32,), 1),
+        ('sgd', ((1813764,), (1813764,), (1813764,)), (), 0),
+    ),
+    "la_val": (
+        ('conv3_c1_fwd', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3,), 0),
+        ('conv3_c1_fwd', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3,), 0),
+        ('conv3_fwd', ((1, 112, 112, 80, 16), (24864,), (16,)), (16, 3), 0),
+        ('conv3_fwd', ((1, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 0),
+        ('conv3_fwd', ((1, 28, 28, 20, 64), (397344,), (64,)), (64, 3), 0),
+        ('conv3_fwd', ((1, 56, 56, 40, 32), (99360,), (32,)), (32, 3), 0),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 0),
+        ('conv3_fwd', ((4, 112, 112, 80, 16), (24864,), (16,)), (16, 3), 0),
+        ('conv3_fwd', ((4, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 0),
+        ('conv3_fwd', ((4, 28, 28, 20, 64), (397344,), (64,)), (64, 3), 0),
+        ('conv3_fwd', ((4, 56, 56, 40, 32), (99360,), (32,)), (32, 3), 0),
+        ('conv3_fwd', ((4, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 0),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 0),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 0),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 0),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 0),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 0),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 0),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 0),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 0),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('norm_eval', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('norm_eval', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('norm_eval', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('norm_eval', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('norm_eval', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('norm_eval', ((4, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('norm_eval', ((4, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('norm_eval', ((4, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('norm_eval', ((4, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('norm_eval', ((4, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('overlap_counts', ((112, 112, 96), (112, 112, 96)), (0,), 0),
+        ('pw16_fwd', ((1, 112, 112, 80, 16), (2, 16, 1, 1, 1), (2,)), (2,), 0),
+        ('pw16_fwd', ((4, 112, 112, 80, 16), (2, 16, 1, 1, 1), (2,)), (2,), 0),
+        ('sw_accumulate', ((112, 112, 80, 2), (112, 112, 96), (112, 112, 96)), (), 0),
+        ('sw_finish', ((112, 112, 96), (112, 112, 96)), (), 0),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 0),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 0),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 0),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 0),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 0),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 0),
+        ('up_fwd', ((4, 56, 56, 40, 32), (4096,), (16,)), (16,), 0),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 0),
+    ),
+    "pancreas_val": (
+        ('conv3_c1_fwd', ((1, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3,), 0),
+        ('conv3_c1_fwd', ((4, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3,), 0),
+        ('conv3_fwd', ((1, 12, 12, 12, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((1, 24, 24, 24, 64), (397344,), (64,)), (64, 3), 1),
+        ('conv3_fwd', ((1, 6, 6, 6, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((4, 12, 12, 12, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((4, 6, 6, 6, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd_stats', ((1, 12, 12, 12, 128), (1589280,), (128,)), (128, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 24, 24, 24, 64), (397344,), (64,)), (64, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 48, 48, 48, 32), (99360,), (32,)), (32, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 6, 6, 6, 256), (6357024,), (256,)), (256, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 96, 96, 96, 16), (24864,), (16,)), (16, 3, 1), 1),
+        ('conv3_fwd_stats', ((4, 12, 12, 12, 128), (1589280,), (128,)), (128, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 24, 24, 24, 64), (397344,), (64,)), (64, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 48, 48, 48, 32), (99360,), (32,)), (32, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 6, 6, 6, 256), (6357024,), (256,)), (256, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 96, 96, 96, 16), (24864,), (16,)), (16, 3, 4), 1),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('down_fwd', ((1, 12, 12, 12, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((1, 24, 24, 24, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((1, 48, 48, 48, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((1, 96, 96, 96, 16), (4096,), (32,)), (32,), 1),
+        ('down_fwd', ((4, 12, 12, 12, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((4, 24, 24, 24, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((4, 48, 48, 48, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((4, 96, 96, 96, 16), (4096,), (32,)), (32,), 1),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('norm_fwd', ((1, 12, 12, 12, 128),), (1, 1), 0),
+        ('norm_fwd', ((1, 24, 24, 24, 64),), (1, 1), 0),
+        ('norm_fwd', ((1, 48, 48, 48, 32),), (1, 1), 0),
+        ('norm_fwd', ((1, 6, 6, 6, 256),), (1, 1), 0),
+        ('norm_fwd', ((1, 96, 96, 96, 16),), (1, 1), 0),
+        ('norm_fwd', ((4, 12, 12, 12, 128),), (4, 1), 0),
+        ('norm_fwd', ((4, 24, 24, 24, 64),), (4, 1), 0),
+        ('norm_fwd', ((4, 48, 48, 48, 32),), (4, 1), 0),
+        ('norm_fwd', ((4, 6, 6, 6, 256),), (4, 1), 0),
+        ('norm_fwd', ((4, 96, 96, 96, 16),), (4, 1), 0),
+        ('overlap_counts', ((96, 96, 112), (96, 96, 112)), (0,), 0),
+        ('pw16_fwd', ((1, 96, 96, 96, 16), (2, 16, 1, 1, 1), (2,)), (2,), 1),
+        ('pw16_fwd', ((4, 96, 96, 96, 16), (2, 16, 1, 1, 1), (2,)), (2,), 1),
+        ('sw_accumulate', ((96, 96, 96, 2), (96, 96, 112), (96, 96, 112)), (), 0),
+        ('sw_finish', ((96, 96, 112), (96, 96, 112)), (), 0),
+        ('up_fwd', ((1, 12, 12, 12, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((1, 24, 24, 24, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((1, 48, 48, 48, 32), (4096,), (16,)), (16,), 1),
+        ('up_fwd', ((1, 6, 6, 6, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((4, 12, 12, 12, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((4, 24, 24, 24, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((4, 48, 48, 48, 32), (4096,), (16,)), (16,), 1),
+        ('up_fwd', ((4, 6, 6, 6, 256), (262144,), (128,)), (128,), 1),
+    ),
+    "acdc_val": (
+        ('bilinear2x_fwd', ((1, 1, 128, 128, 16), (1, 1, 256, 256, 32)), (16,), 0),
+        ('bilinear2x_fwd', ((1, 1, 16, 16, 128), (1, 1, 32, 32, 256)), (128,), 0),
+        ('bilinear2x_fwd', ((1, 1, 32, 32, 64), (1, 1, 64, 64, 128)), (64,), 0),
+        ('bilinear2x_fwd', ((1, 1, 64, 64, 32), (1, 1, 128, 128, 64)), (32,), 0),
+        ('bilinear2x_fwd', ((16, 1, 128, 128, 16), (16, 1, 256, 256, 32)), (16,), 0),
+        ('bilinear2x_fwd', ((16, 1, 16, 16, 128), (16, 1, 32, 32, 256)), (128,), 0),
+        ('bilinear2x_fwd', ((16, 1, 32, 32, 64), (16, 1, 64, 64, 128)), (64,), 0),
+        ('bilinear2x_fwd', ((16, 1, 64, 64, 32), (16, 1, 128, 128, 64)), (32,), 0),
+        ('conv3_c1_fwd', ((1, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1,), 0),
+        ('conv3_c1_fwd', ((16, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1,), 0),
+        ('conv3_fwd', ((1, 1, 128, 128, 16), (17440,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((1, 1, 128, 128, 32), (34848,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((1, 1, 128, 128, 64), (69664,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((1, 1, 16, 16, 128), (1114144,), (256,)), (256, 1), 0),
+        ('conv3_fwd', ((1, 1, 16, 16, 256), (2228256,), (256,)), (256, 1), 0),
+        ('conv3_fwd', ((1, 1, 256, 256, 16), (8736,), (16,)), (16, 1), 0),
+        ('conv3_fwd', ((1, 1, 256, 256, 16), (8736,), (4,)), (4, 1), 0),
+        ('conv3_fwd', ((1, 1, 256, 256, 32), (17440,), (16,)), (16, 1), 0),
+        ('conv3_fwd', ((1, 1, 32, 32, 128), (557088,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((1, 1, 32, 32, 256), (1114144,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((1, 1, 32, 32, 64), (278560,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((1, 1, 64, 64, 128), (278560,), (64,)), (64, 1), 0),
+        ('conv3_fwd', ((1, 1, 64, 64, 32), (69664,), (64,)), (64, 1), 0),
+        ('conv3_fwd', ((1, 1, 64, 64, 64), (139296,), (64,)), (64, 1), 0),
+        ('conv3_fwd', ((16, 1, 128, 128, 16), (17440,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((16, 1, 128, 128, 32), (34848,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((16, 1, 128, 128, 64), (69664,), (32,)), (32, 1), 0),
+        ('conv3_fwd', ((16, 1, 16, 16, 128), (1114144,), (256,)), (256, 1), 0),
+        ('conv3_fwd', ((16, 1, 16, 16, 256), (2228256,), (256,)), (256, 1), 0),
+        ('conv3_fwd', ((16, 1, 256, 256, 16), (8736,), (16,)), (16, 1), 0),
+        ('conv3_fwd', ((16, 1, 256, 256, 16), (8736,), (4,)), (4, 1), 0),
+        ('conv3_fwd', ((16, 1, 256, 256, 32), (17440,), (16,)), (16, 1), 0),
+        ('conv3_fwd', ((16, 1, 32, 32, 128), (557088,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((16, 1, 32, 32, 256), (1114144,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((16, 1, 32, 32, 64), (278560,), (128,)), (128, 1), 0),
+        ('conv3_fwd', ((16, 1, 64, 64, 128), (278560,), (64,)), (64, 1), 0),
+        ('conv3_fwd', ((16, 1, 64, 64, 32), (69664,), (64,)), (64, 1), 0),
+        ('conv3_fwd', ((16, 1, 64, 64, 64), (139296,), (64,)), (64, 1), 0),
+        ('conv3_pack_many', ((720,),), (18,), 0),
+        ('copy_channels', ((1, 1, 128, 128, 32), (1, 1, 128, 128, 64)), (32, 0, 0), 0),
+        ('copy_channels', ((1, 1, 256, 256, 16), (1, 1, 256, 256, 32)), (16, 0, 0), 0),
+        ('copy_channels', ((1, 1, 32, 32, 128), (1, 1, 32, 32, 256)), (128, 0, 0), 0),
+        ('copy_channels', ((1, 1, 64, 64, 64), (1, 1, 64, 64, 128)), (64, 0, 0), 0),
+        ('copy_channels', ((16, 1, 128, 128, 32), (16, 1, 128, 128, 64)), (32, 0, 0), 0),
+        ('copy_channels', ((16, 1, 256, 256, 16), (16, 1, 256, 256, 32)), (16, 0, 0), 0),
+        ('copy_channels', ((16, 1, 32, 32, 128), (16, 1, 32, 32, 256)), (128, 0, 0), 0),
+        ('copy_channels', ((16, 1, 64, 64, 64), (16, 1, 64, 64, 128)), (64, 0, 0), 0),
+        ('k2_pack_many', ((256,),), (4,), 0),
+        ('maxpool2d_fwd', ((1, 1, 128, 128, 32),), (), 0),
+        ('maxpool2d_fwd', ((1, 1, 256, 256, 16),), (), 0),
+        ('maxpool2d_fwd', ((1, 1, 32, 32, 128),), (), 0),
+        ('maxpool2d_fwd', ((1, 1, 64, 64, 64),), (), 0),
+        ('maxpool2d_fwd', ((16, 1, 128, 128, 32),), (), 0),
+        ('maxpool2d_fwd', ((16, 1, 256, 256, 16),), (), 0),
+        ('maxpool2d_fwd', ((16, 1, 32, 32, 128),), (), 0),
+        ('maxpool2d_fwd', ((16, 1, 64, 64, 64),), (), 0),
+        ('norm_eval', ((1, 1, 128, 128, 32), (32,), (32,)), (2,), 0),
+        ('norm_eval', ((1, 1, 16, 16, 256), (256,), (256,)), (2,), 0),
+        ('norm_eval', ((1, 1, 256, 256, 16), (16,), (16,)), (2,), 0),
+        ('norm_eval', ((1, 1, 32, 32, 128), (128,), (128,)), (2,), 0),
+        ('norm_eval', ((1, 1, 64, 64, 64), (64,), (64,)), (2,), 0),
+        ('norm_eval', ((16, 1, 128, 128, 32), (32,), (32,)), (2,), 0),
+        ('norm_eval', ((16, 1, 16, 16, 256), (256,), (256,)), (2,), 0),
+        ('norm_eval', ((16, 1, 256, 256, 16), (16,), (16,)), (2,), 0),
+        ('norm_eval', ((16, 1, 32, 32, 128), (128,), (128,)), (2,), 0),
+        ('norm_eval', ((16, 1, 64, 64, 64), (64,), (64,)), (2,), 0),
+        ('overlap_counts', ((17, 256, 256), (17, 256, 256)), (1,), 0),
+        ('overlap_counts', ((17, 256, 256), (17, 256, 256)), (2,), 0),
+        ('overlap_counts', ((17, 256, 256), (17, 256, 256)), (3,), 0),
+        ('plabel_argmax4', ((1, 1, 256, 256, 4),), (), 0),
+        ('plabel_argmax4', ((16, 1, 256, 256, 4),), (), 0),
+        ('pw_fwd', ((1, 1, 128, 128, 32), (512,), (16,)), (16,), 0),
+        ('pw_fwd', ((1, 1, 16, 16, 256), (32768,), (128,)), (128,), 0),
+        ('pw_fwd', ((1, 1, 32, 32, 128), (8192,), (64,)), (64,), 0),
+        ('pw_fwd', ((1, 1, 64, 64, 64), (2048,), (32,)), (32,), 0),
+        ('pw_fwd', ((16, 1, 128, 128, 32), (512,), (16,)), (16,), 0),
+        ('pw_fwd', ((16, 1, 16, 16, 256), (32768,), (128,)), (128,), 0),
+        ('pw_fwd', ((16, 1, 32, 32, 128), (8192,), (64,)), (64,), 0),
+        ('pw_fwd', ((16, 1, 64, 64, 64), (2048,), (32,)), (32,), 0),
+    ),
+    "la8": (
+        ('conv3_c1_norm_bwd_wgrad', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0),
+        ('conv3_c1_norm_fwd', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0),
+        ('conv3_dgrad_bwdstats', ((4, 28, 28, 20, 64), (397344,), (4, 28, 28, 20, 64)), (64, 3, 1), 1),
+        ('conv3_dgrad_bwdstats', ((4, 56, 56, 40, 32), (99360,), (4, 56, 56, 40, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((4, 112, 112, 80, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd_raw', ((4, 14, 14, 10, 128), (1589280,)), (128, 3, 2), 1),
+        ('conv3_fwd_raw', ((4, 7, 7, 5, 256), (6357024,)), (256, 3, 8), 1),
+        ('conv3_fwd_stats', ((4, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 2), 1),
+        ('conv3_fwd_stats', ((4, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 2), 1),
+        ('conv3_fwd_stats', ((4, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 2), 1),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('conv3_wgrad', ((4, 112, 112, 80, 16), (4, 112, 112, 80, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((4, 14, 14, 10, 128), (4, 14, 14, 10, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((4, 28, 28, 20, 64), (4, 28, 28, 20, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((4, 56, 56, 40, 32), (4, 56, 56, 40, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((4, 7, 7, 5, 256), (4, 7, 7, 5, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((4, 14, 14, 10, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((4, 28, 28, 20, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((4, 56, 56, 40, 32), (4096,)), (16,), 1),
+        ('down_dgrad', ((4, 7, 7, 5, 256), (262144,)), (128,), 1),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('ema', ((9457332,), (9457332,)), (), 0),
+        ('k2_fwd_stats', ((4, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 2), 1),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('k2_wgrad', ((4, 112, 112, 80, 16), (4, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((4, 14, 14, 10, 128), (4, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((4, 14, 14, 10, 128), (4, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((4, 28, 28, 20, 64), (4, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((4, 28, 28, 20, 64), (4, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((4, 56, 56, 40, 32), (4, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((4, 56, 56, 40, 32), (4, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((4, 7, 7, 5, 256), (4, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('mix_box', ((2, 112, 112, 80, 1), (2, 112, 112, 80, 1)), (), 0),
+        ('mixloss_pair_bwd', ((4, 112, 112, 80, 2), (2, 112, 112, 80), (2, 112, 112, 80)), (0,), 0),
+        ('mixloss_pair_fwd', ((4, 112, 112, 80, 2), (2, 112, 112, 80), (2, 112, 112, 80)), (0,), 0),
+        ('norm_bwd', ((4, 112, 112, 80, 16), (4, 112, 112, 80, 16), (5, 2, 16)), (2, 1, True), 0),
+        ('norm_bwd', ((4, 14, 14, 10, 128), (4, 14, 14, 10, 128), (5, 2, 128)), (2, 1, True), 0),
+        ('norm_bwd', ((4, 28, 28, 20, 64), (4, 28, 28, 20, 64), (5, 2, 64)), (2, 1, True), 0),
+        ('norm_bwd', ((4, 56, 56, 40, 32), (4, 56, 56, 40, 32), (5, 2, 32)), (2, 1, True), 0),
+        ('norm_bwd', ((4, 7, 7, 5, 256), (4, 7, 7, 5, 256), (5, 2, 256)), (2, 1, True), 0),
+        ('norm_bwd_slabs', ((4, 14, 14, 10, 128), (2, 4, 14, 14, 10, 128), (5, 2, 128)), (2, 2, 1), 0),
+        ('norm_bwd_slabs', ((4, 7, 7, 5, 256), (8, 4, 7, 7, 5, 256), (5, 2, 256)), (8, 2, 1), 0),
+        ('norm_fwd', ((4, 112, 112, 80, 16), (16,), (16,)), (2, 1), 0),
+        ('norm_fwd', ((4, 14, 14, 10, 128), (128,), (128,)), (2, 1), 0),
+        ('norm_fwd', ((4, 28, 28, 20, 64), (64,), (64,)), (2, 1), 0),
+        ('norm_fwd', ((4, 56, 56, 40, 32), (32,), (32,)), (2, 1), 0),
+        ('norm_fwd', ((4, 7, 7, 5, 256), (256,), (256,)), (2, 1), 0),
+        ('norm_fwd_slabs', ((2, 4, 14, 14, 10, 128), (128,), (128,)), (2, 2, 1), 0),
+        ('norm_fwd_slabs', ((8, 4, 7, 7, 5, 256), (256,), (256,)), (8, 2, 1), 0),
+        ('plabel_cc_largest', ((4, 112, 112, 80, 2),), (3,), 0),
+        ('pw16_bwd_norm_bwd', ((4, 112, 112, 80, 16), (5, 2, 16), (4, 16)), (2, 1), 0),
+        ('pw16_fwd_norm', ((4, 112, 112, 80, 16), (5, 2, 16), (4, 16)), (2, 1, 2), 0),
+        ('sgd', ((9448868,), (9448868,), (9448868,)), (), 0),
+        ('up_dgrad', ((4, 112, 112, 80, 16), (4096,)), (32,), 1),
+        ('up_dgrad', ((4, 14, 14, 10, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((4, 28, 28, 20, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((4, 56, 56, 40, 32), (16384,)), (64,), 1),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+    ),
 }
 
 TAU = 2.0 ** -14            # elementwise bound for convolutions, GEMMs and norms: |out - ref64| <= TAU * cond
 TAU_OPT = 2.0 ** -22        # optimiser / EMA updates: |out - ref64| <= TAU_OPT * (|p| + |update|)
 TAU_ADAM = 2.0 ** -21       # Adam's update goes through six fp32 roundings (sqrt, / bc2, + eps, m / den, lr / bc1, the product): up to
                             # ~6 * 2^-24 of |update|; 1.3 * 2^-22 measured on the device and on the simulator (correctly rounded host math)
-STEP_GROUPS = 2             # every product step runs its networks grouped 2 (norm statistics per group of samples)
+TAU_NORM_EVAL = 2.0 ** -20  # norm_eval: nine fp32 roundings (rv + eps, sqrt, 1 / ., gamma * ., y - rm, * scale, + beta, the LeakyReLU slope and
+                            # its 0.01f, + residual): up to ~9.4 * 2^-24 of cond -> the power of two above
+STEP_GROUPS = 2             # every self-training step runs its networks grouped 2 (norm statistics per group of samples)
 EPS = 1e-5
+
+
+def network_of(wl):
+    """the workload whose network (and configuration) `wl` runs: la_pre, la_val, la8 -> la"""
+    return "la" if wl == "la8" else wl.partition("_")[0]
+
+
+def stats_fused(wl, key):
+    """whether `wl` feeds the norm behind the conv3_fwd_stats launch `key` from its fused partials: STEP_VARIANTS has a 'partial'
+    epilogue at the norm key of the conv's output"""
+    ys = tuple(key[1][0][:-1]) + (key[2][0],)
+    return any(k[0] == "norm_fwd" and tuple(k[1][0]) == ys and any("partial" in f for f in fl) for k, fl in STEP_VARIANTS.get(wl, {}).items())
+
+
+def step_groups(wl):
+    """norm groups of the workload's network calls: 2 in the self-training steps; pre-training calls the network without groups="""
+    return 1 if wl.endswith(("_pre", "_val")) else STEP_GROUPS
 
 
 def _acts(act, z):
@@ -516,8 +1055,12 @@ def _pre_norm(g, shape):
     return (torch.randn(shape, generator=g, dtype=torch.float64) * sc + off).float()
 
 
-def drive_conv(ops, dev, key, g):
-    """conv3_fwd / conv3_fwd_stats / conv3_fwd_raw / conv3_dgrad_bwdstats: the output against sum over 27 (9) shifted matmuls in fp64"""
+def drive_conv(ops, dev, key, g, groups=STEP_GROUPS, fused=True):
+    """conv3_fwd / conv3_fwd_stats / conv3_fwd_raw / conv3_dgrad_bwdstats: the output against sum over 27 (9) shifted matmuls in fp64,
+    sample by sample (the reference of an N = 4 validation chunk is the cost of its row).  namax == 0 (the validation pass: norm_eval
+    leaves no |max| on its output): the operand must reach the library without one and the launch must not take the two-plane fp16 instance.
+    fused (conv3_fwd_stats): whether the pass feeds the norm behind from this launch's statistics partials (stats_fused) -- the
+    pancreas validation pass calls conv3_fwd_stats at every level and gets none at the small ones, where the call is a plain conv"""
     from bcp_amd import hip_ops as H
     op, shapes, ints, namax = key
     xs = shapes[0]
@@ -534,7 +1077,7 @@ def drive_conv(ops, dev, key, g):
         if namax:
             _amax(H, xd, dev)
         yp = _pre_norm(g, shapes[2]).to(dev)
-        act, Gn = ints[2], STEP_GROUPS       # (the key's ints are Cin, KD, act: the groups argument comes fourth)
+        act, Gn = ints[2], groups            # (the key's ints are Cin, KD, act: the groups argument comes fourth)
         C = yp.shape[-1]
         gam = (torch.rand(C, generator=g) + 0.5).to(dev)
         bet = (torch.rand(C, generator=g) - 0.5).to(dev)
@@ -569,7 +1112,7 @@ def drive_conv(ops, dev, key, g):
             res = ops.conv3_fwd(xd, wf, b, Cout, KD)
         elif op == "conv3_fwd_stats":
             res, part, rows = ops.conv3_fwd_stats(xd, wf, b, Cout, KD, ints[2])
-            assert rows > 0 or dev.type == "cpu", f"{op} {xs}: no fused statistics at the step's shape"
+            assert (rows > 0) == fused or dev.type == "cpu", f"{op} {xs}: {rows} rows of fused statistics at the step's shape, the pass {'uses' if fused else 'has none'}"
         elif op == "conv3_fwd_raw":
             nsl = ops.conv3_nslabs(xs, Cout, KD)          # (ints[2] at the in-step shape; the reduced simulator shapes may not be served raw)
             assert nsl == ints[2] or dev.type == "cpu", f"{op} {xs}: {nsl} split-K slabs, the step launches {ints[2]}"
@@ -577,17 +1120,25 @@ def drive_conv(ops, dev, key, g):
         else:
             raise KeyError(op)
         wk = w.double()
+    if not namax:
+        assert ops._amax_of(xd) is None, f"{op} {xs}: the operand carries a |max| the step's does not"
+        sec = int(ops.b.call("bcp_conv3_last_section"))        # (4: the launch read the two-plane fp16 section of the pack)
+        assert sec != 4, f"{op} {xs}: an operand without |max| took the two-plane fp16 instance"
     xc = x.double()
     if two_d:
         wk = wk.reshape(wk.shape[0], wk.shape[1], 3, 3)
-    ref = conv3_cl64(xc, wk)
-    cond = conv3_cl64(xc.abs(), wk.abs())
-    if op in ("conv3_fwd", "conv3_fwd_stats") and b is not None:
-        ref += b.double().cpu()
-        cond += b.double().cpu().abs()
     tile = (1, 16, 16) if two_d else (4, 8, 8)
     rc = res.cpu()
-    out.append((op, check_elementwise(rc, ref, cond, TAU, f"{op} {xs}", tile)))
+    worst = None
+    for n in range(xs[0]):
+        ref = conv3_cl64(xc[n:n + 1], wk)
+        cond = conv3_cl64(xc[n:n + 1].abs(), wk.abs())
+        if op in ("conv3_fwd", "conv3_fwd_stats") and b is not None:
+            ref += b.double().cpu()
+            cond += b.double().cpu().abs()
+        r = check_elementwise(rc[n:n + 1], ref, cond, TAU, f"{op} {xs} sample {n}", tile)
+        worst = r if worst is None or r[0] > worst[0] else worst
+    out.append((op, worst))
     if op == "conv3_fwd_stats" and rows:
         # the fused statistics partials: fp64 column sums / sums of squares of the kernel's own output, per group
         Gn = ints[2]
@@ -1059,6 +1610,8 @@ def drive_k2(ops, dev, key, g, variants=((),)):
         xd = x.to(dev)
         if namax:
             _amax(H, xd, dev)
+        else:
+            assert ops._amax_of(xd) is None, f"{tag}: the operand carries a |max| the pass's does not"
         b = (torch.randn(Co, generator=g) * 0.1) if fwd else None
         bd = None if b is None else b.to(dev)
         # the layer's own weight: Conv3d [Cout, Cin, 2, 2, 2] (down, 1x1) or ConvTranspose3d [Cin, Cout, 2, 2, 2] (up); a dgrad maps Cout -> Cin
@@ -1254,6 +1807,7 @@ _NETS = {}
 
 def _step_network(wl, dev, ops):
     """the workload's student network as its factory builds it for make_step (net_factory / BCP_net / create_Vnet), on `dev`, bound to `ops`"""
+    wl = network_of(wl)
     net = _NETS.get((wl, dev.type))
     if net is None:
         torch.manual_seed(1337)
@@ -1559,6 +2113,307 @@ def drive_mixloss(ops, dev, key, g, variants=((),)):
     return out
 
 
+# -------------------------------------------------------------------------------------------------- the validation passes' ops
+
+
+def norm_eval_ref64(y, gamma, beta, rm, rv, act, residual=None, eps=EPS):
+    """fp64 eval-mode BatchNorm: act((y - rm) * gamma / sqrt(rv + eps) + beta) [+ residual] -> (a, pre-activation z, cond, its part
+    in front of the activation); eps as the kernel receives it (fp32)"""
+    y, gamma, beta, rm, rv = (t.double().cpu() for t in (y, gamma, beta, rm, rv))
+    sc = gamma / torch.sqrt(rv + float(np.float32(eps)))
+    z = (y - rm) * sc + beta
+    a, _ = _acts(act, z)
+    zcond = (y - rm).abs() * sc.abs() + beta.abs()
+    cond = zcond.clone()
+    if residual is not None:
+        a = a + residual.double().cpu()
+        cond = cond + residual.double().cpu().abs()
+    return a, z, cond, zcond
+
+
+def drive_norm_eval(ops, dev, key, g, variants=((),)):
+    """norm_eval at the chunk's shape: one launch at the recorded N, the fp64 reference sample by sample.  Running variances over four
+    decades, gamma / beta as the norm drivers draw them, a residual where the pass adds a skip.  An element whose fp64 pre-activation
+    lies within the bound of the activation's kink may take the other branch: there the two branches differ by less than |z|, which is
+    allowed on top (the comparison is then the pre-activation's).  The output must carry no |max|: the convs behind take the
+    three-plane instances."""
+    op, shapes, ints, namax = key
+    ys, act = shapes[0], ints[0]
+    C = ys[-1]
+    tile = (1, 16, 16) if ys[1] == 1 else (4, 8, 8)
+    out = []
+    for flags in variants:
+        tag = f"{op} {ys} [{'+'.join(flags) or 'plain'}]"
+        y = _pre_norm(g, ys)
+        rm = (y.reshape(-1, C)[:4096].double().mean(0) + torch.randn(C, generator=g, dtype=torch.float64) * 0.1).float()
+        rv = torch.pow(10.0, torch.rand(C, generator=g, dtype=torch.float64) * 4 - 2).float()
+        gam, bet = torch.rand(C, generator=g) + 0.5, torch.rand(C, generator=g) - 0.5
+        res = activation(g, ys) if "residual" in flags else None
+        a = ops.norm_eval(y.to(dev), gam.to(dev), bet.to(dev), rm.to(dev), rv.to(dev), act, residual=None if res is None else res.to(dev))
+        assert getattr(a, "_bcp_amax", None) is None, f"{tag}: the output carries a |max|"
+        ac = a.cpu()
+        worst = None
+        for n in range(ys[0]):
+            ref, z, cond, zcond = norm_eval_ref64(y[n:n + 1], gam, bet, rm, rv, act, None if res is None else res[n:n + 1])
+            kink = z.abs() <= TAU_NORM_EVAL * zcond
+            err = ((ac[n:n + 1].double() - ref).abs() - torch.where(kink, z.abs(), torch.zeros_like(z))).clamp_min(0)
+            r = check_elementwise(err, torch.zeros_like(err), cond, TAU_NORM_EVAL, f"{tag} sample {n}", tile)
+            worst = r if worst is None or r[0] > worst[0] else worst
+        out.append((op + ("" if not flags else " " + "+".join(flags)), worst))
+    return out
+
+
+def drive_c1_plain(ops, dev, key, g):
+    """conv3_c1_fwd, the eval-mode first layer (1 -> 16, bias, no norm): fp64 conv sample by sample"""
+    op, shapes, ints, namax = key
+    xs, ws = shapes[0], shapes[1]
+    KD = ints[0]
+    x, w, b = activation(g, xs), _conv_weight(g, 16, 1, KD), torch.randn(16, generator=g) * 0.1
+    assert tuple(w.shape) == tuple(ws), key
+    y = ops.conv3_c1_fwd(x.to(dev), w.to(dev), b.to(dev), KD).cpu()
+    tile = (1, 16, 16) if KD == 1 else (4, 8, 8)
+    worst = None
+    for n in range(xs[0]):
+        ref = conv3_cl64(x[n:n + 1], w) + b.double()
+        cond = conv3_cl64(x[n:n + 1].abs(), w.abs()) + b.double().abs()
+        r = check_elementwise(y[n:n + 1], ref, cond, TAU, f"{op} {xs} sample {n}", tile)
+        worst = r if worst is None or r[0] > worst[0] else worst
+    return [(op, worst)]
+
+
+def drive_pw16(ops, dev, key, g):
+    """pw16_fwd, the eval-mode 16 -> C head on a materialised activation: x @ W^T + b in fp64"""
+    from bcp_amd import hip_ops as H
+    op, shapes, ints, namax = key
+    xs, Cout = shapes[0], ints[0]
+    x = activation(g, xs)
+    w, b = _k2_weight(g, tuple(shapes[1]), 16), torch.randn(Cout, generator=g) * 0.1
+    xd = x.to(dev)
+    if namax:
+        _amax(H, xd, dev)
+    else:
+        assert ops._amax_of(xd) is None, f"{op} {xs}: the operand carries a |max| the pass's does not"
+    lg = ops.pw16_fwd(xd, w.to(dev), b.to(dev), Cout)
+    W = w.double().reshape(Cout, 16)
+    ref, cond = x.double() @ W.t() + b.double(), x.double().abs() @ W.abs().t() + b.double().abs()
+    return [(op, check_elementwise(lg.cpu(), ref, cond, TAU, f"{op} {xs}"))]
+
+
+def drive_copy_channels(ops, dev, key, g):
+    """copy_channels as the eval-mode U-Net fills the skip half of a concat buffer: the first Cc channels bit for bit, the rest untouched"""
+    op, shapes, ints, namax = key
+    xs, ds = shapes[0], shapes[1]
+    Cc, so, do = ints
+    src = activation(g, xs)
+    dst = torch.full(ds, 7.0, device=dev)
+    ops.copy_channels(src.to(dev), dst, Cc, so, do, carry_amax=True)
+    d = dst.cpu()
+    assert torch.equal(d[..., do:do + Cc].contiguous().view(torch.int32), src[..., so:so + Cc].contiguous().view(torch.int32)), f"{op} {xs}: copied channels differ"
+    keep = torch.ones(ds[-1], dtype=torch.bool)
+    keep[do:do + Cc] = False
+    assert bool((d[..., keep] == 7.0).all()), f"{op} {xs}: wrote outside its channels"
+    assert getattr(dst, "_bcp_amax", None) is None, f"{op} {xs}: a source without |max| left one on the buffer"
+    return [(op, (0.0, "exact"))]
+
+
+def sw_origins(vol, patch, stride_xy=18, stride_z=4):
+    """the patch origins of a sliding-window pass in stream order (test_3d_patch.sliding_window_scores: x, y, z nested, the last origin
+    along an axis clamped to extent - patch) over a volume at least as large as the patch"""
+    import math
+    st = (stride_xy, stride_xy, stride_z)
+    n = [math.ceil((v - p) / s) + 1 for v, p, s in zip(vol, patch, st)]
+    return [tuple(min(s * i, v - p) for s, i, v, p in zip(st, ijk, vol, patch))
+            for ijk in ((x, y, z) for x in range(n[0]) for y in range(n[1]) for z in range(n[2]))]
+
+
+def _sw_logits(g, vol, patch, C, origins):
+    """one patch of logits per origin: a volume-wide field uniform on +-12 (as _loss_inputs draws logits) cropped at the origin, plus a
+    per-visit jitter of +-0.5 -- the overlapping patches of a real pass see the same voxels, so a voxel's visits agree up to the
+    network's dependence on the patch position.  (Independent +-12 draws per visit would put a saturated 1 beside a saturated 0 on
+    1.2 % of the twice-visited voxels: an average of exactly 0.5 that no real pass produces, and far over SW_BAND_CAP.)"""
+    field = (torch.rand(vol + (C,), generator=g, dtype=torch.float64) * 2 - 1) * 12
+    return [(field[x:x + patch[0], y:y + patch[1], z:z + patch[2]] + torch.rand(patch + (C,), generator=g, dtype=torch.float64) - 0.5).float()
+            for x, y, z in origins]
+
+
+def sw_ref(logits, origins, vol, cls, dtype=torch.float64):
+    """sliding-window score of class `cls`: softmax per patch, summed over the visits in stream order, divided by the visit count, all in
+    `dtype` (fp64: the reference; fp32: what plain torch arithmetic makes of the same expression) -> (score, integer counts)"""
+    score, cnt = torch.zeros(vol, dtype=dtype), torch.zeros(vol, dtype=torch.int64)
+    for lg, (x, y, z) in zip(logits, origins):
+        px, py, pz = lg.shape[:3]
+        score[x:x + px, y:y + py, z:z + pz] += torch.softmax(lg.to(dtype), -1)[..., cls]
+        cnt[x:x + px, y:y + py, z:z + pz] += 1
+    return score / cnt.to(dtype), cnt
+
+
+# the sliding-window score against fp64, in units of the score itself (a sum of positive terms over a count: cond = the fp64 score).  The
+# same expression in torch fp32 on the host is off by at most TAU_SW_TORCH32 x cond on the driver's inputs (logits uniform on +-12, five
+# visits); TAU_SW = 4 x that, rounded up to a power of two (the rule that set TAU_LOSS).  The kernel: TAU_SW_KERNEL x cond on the device.
+TAU_SW_TORCH32 = 1.09e-6        # = 18.3 x 2^-24 (LA 112 x 112 x 96, class 0; class 1 1.07e-6; pancreas 96 x 96 x 112 1.08e-6): exp() of a logit
+                                # difference up to 25
+TAU_SW_KERNEL = 1.10e-6         # pancreas 96 x 96 x 112, class 1 alone; LA 1.07e-6; the simulator at the reduced LA shape 1.02e-6
+TAU_SW = 2.0 ** -17             # 4 x 1.09e-6 = 4.4e-6 -> 7.63e-6
+SW_BAND_CAP = 1e-4              # at most this share of the voxels may lie within TAU_SW of the threshold (logit differences have density
+                                # 1 / 24 at zero: about 1e-6 of them do)
+
+
+def drive_sw(ops, dev, key, g):
+    """sw_accumulate + sw_finish.  The sw_accumulate row replays a validation pass's origin list (strides 18 / 4: clamped last origins,
+    overlapping patches, stream order) on logits spread over +-12, once with class 1 into one map (LA) and once with classes 0 and 1
+    into two maps sharing the first one's counts (pancreas): counts exact, scores elementwise to TAU_SW x score, the label bit for bit
+    `kernel score > 0.5` and equal to the fp64 label outside the band |ref - 0.5| <= TAU_SW.  The sw_finish row divides planted
+    quotients: exact halves (label 0: the rule is >, not >=), their upper neighbours (label 1), zeros."""
+    op, shapes, ints, namax = key
+    vol = tuple(shapes[1] if op == "sw_accumulate" else shapes[0])
+    out = []
+    if op == "sw_finish":
+        cnt = torch.randint(1, 6, vol, generator=g).float()
+        score = (torch.rand(vol, generator=g, dtype=torch.float64) * cnt.double()).float()
+        flat, cf = score.view(-1), cnt.view(-1)
+        half = torch.arange(0, flat.numel(), 7)
+        flat[half] = 0.5 * cf[half]                                                     # exact quotient 0.5 for every count
+        up = half[: half.numel() // 2] + 1
+        flat[up] = torch.nextafter(torch.tensor(0.5), torch.tensor(1.0)) * cf[up]
+        flat[half[: half.numel() // 3] + 2] = 0.0
+        ref = score.double() / cnt.double()
+        sd = score.clone().to(dev)
+        lab = ops.sw_finish(sd, cnt.to(dev), 0.5).cpu()
+        sk = sd.cpu()
+        res = check_elementwise(sk, ref, ref, 2.0 ** -24, f"{op} {vol} quotient")         # (one correctly rounded division)
+        assert torch.equal(lab, (sk > 0.5).to(torch.uint8)), f"{op} {vol}: label differs from kernel score > 0.5"
+        assert bool((sk.view(-1)[half] == 0.5).all()) and not bool(lab.view(-1)[half].any()), f"{op} {vol}: an exact 0.5 was labelled 1"
+        far = (ref - 0.5).abs() > TAU_SW
+        assert torch.equal(lab[far], (ref > 0.5).to(torch.uint8)[far]), f"{op} {vol}: label differs from the fp64 label outside the band"
+        return [(op, res)]
+    patch, C = tuple(shapes[0][:3]), shapes[0][3]
+    origins = sw_origins(vol, patch)
+    for classes in ((1,), (0, 1)):
+        tag = f"{op} {vol} patch {patch} classes {classes}"
+        logits = _sw_logits(g, vol, patch, C, origins)
+        refs = [sw_ref(logits, origins, vol, c) for c in classes]
+        for c, (r64, _) in zip(classes, refs):
+            band = float(((r64 - 0.5).abs() <= TAU_SW).double().mean())
+            assert band <= SW_BAND_CAP, f"{tag}: {band:.2e} of the fp64 scores of class {c} lie within the bound of the threshold"
+        scores = [torch.zeros(vol, device=dev) for _ in classes]
+        cnt = torch.zeros(vol, device=dev)
+        scratch = torch.zeros(vol, device=dev)
+        for lg, org in zip(logits, origins):
+            ld = lg.to(dev)
+            for ci, c in enumerate(classes):
+                ops.sw_accumulate(ld, scores[ci], cnt if ci == 0 else scratch, org, cls=c)
+        assert torch.equal(cnt.cpu().long(), refs[0][1]), f"{tag}: visit counts differ"
+        for ci, c in enumerate(classes):
+            r64 = refs[ci][0]
+            lab = ops.sw_finish(scores[ci], cnt, 0.5).cpu()
+            sk = scores[ci].cpu()
+            r32, _ = elementwise_ratio(sw_ref(logits, origins, vol, c, torch.float32)[0].double(), r64, r64)
+            res = check_elementwise(sk, r64, r64, TAU_SW, f"{tag} class {c}")
+            print(f"[product-op] {tag} class {c}: torch fp32 is off by {r32:.3e} x cond ({r32 / 2.0 ** -24:.2f} x 2^-24), the kernel by "
+                  f"{res[0] * TAU_SW:.3e} x cond")
+            assert torch.equal(lab, (sk > 0.5).to(torch.uint8)), f"{tag} class {c}: label differs from kernel score > 0.5"
+            far = (r64 - 0.5).abs() > TAU_SW
+            assert torch.equal(lab[far], (r64 > 0.5).to(torch.uint8)[far]), f"{tag} class {c}: label differs from the fp64 label outside the band"
+            out.append((f"{op} cls{c}/{len(classes)}", res))
+    return out
+
+
+def overlap_ref(pred, gt, cls):
+    """{|A & B|, |A|, |B|} in numpy integers (A = pred != 0, or == cls where cls > 0; B = gt likewise)"""
+    p, q = np.asarray(pred).reshape(-1), np.asarray(gt).reshape(-1)
+    a, b = ((p == cls), (q == cls)) if cls else ((p != 0), (q != 0))
+    return [int(np.count_nonzero(a & b)), int(np.count_nonzero(a)), int(np.count_nonzero(b))]
+
+
+def drive_overlap(ops, dev, key, g):
+    """overlap_counts on cc_maps pairs at the recorded size (binary maps for cls 0, three classes in bands for the ACDC classes), then on
+    prefixes whose length is no multiple of 64 or 256, and lengths on both sides of the grid cap (2048 blocks of 256): exact"""
+    op, shapes, ints, namax = key
+    vol, cls = tuple(shapes[0]), ints[0]
+    two_d = cls > 0                                                     # ACDC: [slices, H, W]
+    maps = [m for _, m in cc_maps(((vol[0], 1) + vol[1:]) if two_d else ((1,) + vol), g, two_d=two_d)]
+    if two_d:
+        W = vol[2]
+        maps = [(m.long() * (1 + (torch.arange(W) * 3 // max(W, 1)).view(1, 1, 1, W))).clamp(max=3).to(torch.uint8) for m in maps]
+    maps = [m.reshape(vol).contiguous() for m in maps]
+    n = maps[0].numel()
+    cap = 2048 * 256
+    lens = sorted({n - 1, n - vol[-1] - 37, 255, 257, cap - 1, cap + 1, cap + 257} & set(range(1, n)))
+    for i, (p, q) in enumerate(((maps[0], maps[1]), (maps[1], maps[2]), (maps[2], maps[0]))):
+        got = ops.overlap_counts(p.to(dev), q.to(dev), cls).tolist()
+        assert got == overlap_ref(p, q, cls), f"{op} {vol} cls {cls} pair {i}: {got} != {overlap_ref(p, q, cls)}"
+        for L in lens if i == 0 else ():
+            pf, qf = p.reshape(-1)[:L].contiguous(), q.reshape(-1)[:L].contiguous()
+            got = ops.overlap_counts(pf.to(dev), qf.to(dev), cls).tolist()
+            assert got == overlap_ref(pf, qf, cls), f"{op} length {L} cls {cls}: {got} != {overlap_ref(pf, qf, cls)}"
+    return [(op, (0.0, "exact"))]
+
+
+def drive_argmax4(ops, dev, key, g):
+    """plabel_argmax4 bit for bit against torch.argmax on the same fp32 logits, with planted exact ties (two, three and all four
+    channels equal at the maximum): the first index wins"""
+    op, shapes, ints, namax = key
+    ls = shapes[0]
+    lg = ((torch.rand(ls, generator=g, dtype=torch.float64) * 2 - 1) * 12).float()
+    flat = lg.view(-1, 4)
+    top = flat.max(1).values
+    idx = torch.arange(0, flat.shape[0], 5)
+    for j, sel in enumerate((idx[0::3], idx[1::3], idx[2::3])):
+        ch = [(3, 1), (0, 2, 3), (0, 1, 2, 3)][j]
+        for c in ch:
+            flat[sel, c] = top[sel]
+    ref = torch.argmax(lg, -1).to(torch.uint8)
+    o = ops.plabel_argmax4(lg.to(dev)).cpu()
+    assert torch.equal(o, ref), f"{op} {ls}: {int((o != ref).sum())} voxels differ from torch.argmax"
+    return [(op, (0.0, "exact"))]
+
+
+def mixloss64(logits, img_l, patch_l, box6, flavour, weights, dtype=torch.float64):
+    """closed form of ONE mix_loss call (the pre-training loss): the first half of mixloss_pair64 on the batch doubled ->
+    (out3, d ((dice + ce) / 2) / d logits, cond of that gradient)"""
+    N = logits.shape[0]
+    o6, _, gr, cond = mixloss_pair64(torch.cat([logits, logits]), ((img_l, patch_l), (img_l, patch_l)), box6, flavour, (weights, weights), dtype)
+    return o6[0], gr[:N], cond[:N]
+
+
+def drive_mixloss_single(ops, dev, key, g, variants=((),)):
+    """mixloss_fwd / mixloss_bwd as the pre-training steps call them.  LA / pancreas (flavour 0, sup_loss_parts): both label arguments
+    the same map, the all-zero box, weights (1, 0) -- CE and Dice over the whole volume.  ACDC (flavour 1, acdc_mix_loss(u_weight=1.0,
+    unlab=True)): image and patch labels, a real box, weights (1, 1).  out3 to 1e-5, the gradient (upstream gradients on the device,
+    0.5 each: loss = (dice + ce) / 2) elementwise to TAU_LOSS x cond."""
+    op, shapes, ints, namax = key
+    ls, flavour = shapes[0], ints[0]
+    N, C = ls[0], ls[-1]
+    sp = tuple(ls[1:4])
+    tile = (1, 16, 16) if sp[0] == 1 else (4, 8, 8)
+    out = []
+    for flags in variants:
+        cases = [((0,) * 6, (1.0, 0.0), True)] if flavour == 0 else [(b, (1.0, 1.0), False) for b in _boxes(sp, g)]
+        for bi, (box6, wts, same) in enumerate(cases):
+            tag = f"{op} {ls} box {box6} [{'+'.join(flags) or 'plain'}]"
+            logits, labs = _loss_inputs(g, (2 * N,) + tuple(ls[1:]), C)
+            logits = logits[:N].contiguous()
+            img_l, patch_l = labs[0][0], (labs[0][0] if same else labs[0][1])
+            o64, g64, c64 = mixloss64(logits, img_l, patch_l, box6, flavour, wts)
+            ld, il, pl = logits.to(dev), img_l.to(dev), patch_l.to(dev)
+            o3, ws = ops.mixloss_fwd(ld, il, pl, box6, flavour, wts[0], wts[1])
+            d3 = float((o3.cpu().double() - o64).abs().max())
+            print(f"[product-op] {tag}: out3 off by {d3:.3e}")
+            assert d3 <= 1e-5, f"{tag}: out3 off by {d3:.3e}"
+            if op == "mixloss_fwd":
+                out.append((f"{op} box{bi}", (d3 / 1e-5, "scalars")))
+                continue
+            up = 0.75
+            if "g_dev" in flags:
+                d = ops.mixloss_bwd(ld, il, pl, box6, flavour, ws, 1.0, 1.0, g_dev=torch.full((2,), 0.5 * up, device=dev))
+            else:
+                d = ops.mixloss_bwd(ld, il, pl, box6, flavour, ws, 0.5 * up, 0.5 * up)
+            res = check_elementwise(d.cpu(), up * g64, up * c64, TAU_LOSS, tag, tile)
+            print(f"[product-op] {tag}: the kernel is off by {res[0] * TAU_LOSS:.3e} x cond")
+            out.append((f"{op} box{bi}", res))
+    return out
+
+
 DRIVERS = {"conv3_fwd": drive_conv, "conv3_fwd_stats": drive_conv, "conv3_fwd_raw": drive_conv, "conv3_dgrad_bwdstats": drive_conv,
            "conv3_wgrad": drive_wgrad, "norm_fwd": drive_norm_fwd, "norm_bwd": drive_norm_bwd,
            "sgd": drive_optim, "ema": drive_optim, "adam": drive_optim,
@@ -1568,7 +2423,10 @@ DRIVERS = {"conv3_fwd": drive_conv, "conv3_fwd_stats": drive_conv, "conv3_fwd_ra
            "k2_wgrad": drive_k2, "pw_fwd": drive_k2, "norm_fwd_slabs": drive_norm_slabs, "norm_bwd_slabs": drive_norm_slabs,
            "mix_box": drive_mix_box, "conv3_pack_many": drive_pack_many, "k2_pack_many": drive_pack_many,
            "conv3_c1_norm_fwd": drive_c1, "conv3_c1_norm_bwd_wgrad": drive_c1, "pw16_fwd_norm": drive_head, "pw16_bwd_norm_bwd": drive_head,
-           "mixloss_pair_fwd": drive_mixloss, "mixloss_pair_bwd": drive_mixloss}
+           "mixloss_pair_fwd": drive_mixloss, "mixloss_pair_bwd": drive_mixloss,
+           "mixloss_fwd": drive_mixloss_single, "mixloss_bwd": drive_mixloss_single, "norm_eval": drive_norm_eval,
+           "conv3_c1_fwd": drive_c1_plain, "pw16_fwd": drive_pw16, "copy_channels": drive_copy_channels,
+           "sw_accumulate": drive_sw, "sw_finish": drive_sw, "overlap_counts": drive_overlap, "plabel_argmax4": drive_argmax4}
 
 
 def table_rows():
@@ -1576,16 +2434,32 @@ def table_rows():
     return [(wl, k) for wl, keys in STEP_KEYS.items() for k in keys]
 
 
+def _row_ident(wl, k):
+    """what makes a row a repeat of an earlier workload's: the key, the flags its calls pass, the norm groups a conv driver runs the
+    layer behind with, and -- for the pack rows, which drive a whole network -- the network"""
+    return (k, tuple(variants_of(wl, k)), step_groups(wl) if k[0] == "conv3_dgrad_bwdstats" else stats_fused(wl, k) if k[0] == "conv3_fwd_stats" else None,
+            network_of(wl) if k[0].endswith("pack_many") else None)
+
+
 def driven_rows():
-    """table rows with a driver, plus norm keys only a statistics-only call uses (the profile does not record those)"""
-    rows = [(wl, k) for wl, k in table_rows() if k[0] in DRIVERS]
-    have = set(rows)
+    """table rows with a driver, plus norm keys only a statistics-only call uses (the profile does not record those); a key that
+    already stands under an earlier workload with the same flags is driven once"""
+    rows, seen = [], set()
+    for wl, k in table_rows():
+        if k[0] in DRIVERS and _row_ident(wl, k) not in seen:
+            seen.add(_row_ident(wl, k))
+            rows.append((wl, k))
     for wl, v in STEP_VARIANTS.items():
-        rows += [(wl, k) for k in v if (wl, k) not in have]
+        for k in v:
+            if k not in STEP_KEYS[wl] and _row_ident(wl, k) not in seen:
+                seen.add(_row_ident(wl, k))
+                rows.append((wl, k))
     return rows
 
 
 def row_id(wl, key):
+    """the row's parametrisation id: workload, op, first shape, int arguments (keys that differ only behind those -- a conv with and
+    without bias -- share it, and pytest numbers them)"""
     op, shapes, ints, _ = key
     return f"{wl}-{op}-" + "x".join(str(v) for v in shapes[0]) + ("-" + "-".join(str(int(i)) for i in ints) if ints else "")
 
@@ -1596,6 +2470,8 @@ def reduce_key(key, f=8):
     op, shapes, ints, namax = key
 
     def red(s):
+        if op in ("sw_accumulate", "sw_finish", "overlap_counts") and len(s) in (3, 4):      # a volume [X, Y, Z] / one patch's logits [px, py, pz, C]
+            return tuple(max(2, e // f) for e in s[:3]) + tuple(s[3:])
         if len(s) == 5:
             N, D, H, W, C = s
             return (N, D if D == 1 else max(2, D // f), max(2, H // f) // 2 * 2, max(2, W // f) // 2 * 2, C)
@@ -1622,7 +2498,7 @@ def reduce_key(key, f=8):
         shapes = tuple(grids[i](s) if i < len(grids) else s for i, s in enumerate(shapes))
         return op, shapes, ints, namax
     # shapes that stay: a weight gradient's, and the weights behind the input of the fused first layer and head
-    first_only = op in ("conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm")
+    first_only = op in ("conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm", "conv3_c1_fwd", "pw16_fwd")
     shapes = tuple(s if (i > 0 and first_only) or (i == 2 and op.endswith("wgrad")) else red(s) for i, s in enumerate(shapes))
     if op == "mix_box":                     # (the kernel takes W * C in fours)
         shapes = tuple(s[:3] + (max(4, s[3] // 4 * 4), s[4]) for s in shapes)
@@ -1641,7 +2517,7 @@ def reduce_key(key, f=8):
 # off the step itself: during the eager recording pass it notes, per key, which epilogue each norm call used.
 _VARIANT_OPS = ("norm_fwd", "norm_bwd", "down_fwd", "down_dgrad", "up_fwd", "up_dgrad", "k2_fwd_stats", "k2_wgrad", "pw_fwd",
                 "norm_fwd_slabs", "norm_bwd_slabs", "mix_box", "conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm",
-                "pw16_bwd_norm_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd")
+                "pw16_bwd_norm_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd", "mixloss_fwd", "mixloss_bwd", "norm_eval")
 _FLAG_ORDER = ("chan_scale", "elem_mask", "partial", "residual", "stats_only", "out_slab", "accumulate", "dw_accumulate",
                "norm_accumulate", "out", "mask", "g_dev")
 
@@ -1696,7 +2572,7 @@ def record_step_variants(workload, names=None):
         setattr(Ops, n, wrap(n, saved[n]))
     try:
         step = make_step(workload, torch.device("cuda:0"))
-        for _ in range(2):
+        for _ in range(max(1, setup_steps(workload))):
             step()
         torch.cuda.synchronize()
     finally:
@@ -1830,6 +2706,249 @@ STEP_VARIANTS = {   # {workload: {key: flag sets the step uses}} (record_step_va
         ('pw_fwd', ((12, 1, 128, 128, 16), (512,)), (32,), 0): ((),),
         ('pw_fwd', ((12, 1, 128, 128, 32), (512,), (16,)), (16,), 1): ((),),
     },
+    "la_pre": {
+        ('conv3_c1_norm_bwd_wgrad', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0): (('accumulate', 'dw_accumulate'),),
+        ('conv3_c1_norm_fwd', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0): ((),),
+        ('down_dgrad', ((1, 14, 14, 10, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 28, 28, 20, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 56, 56, 40, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 7, 7, 5, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('k2_wgrad', ((1, 112, 112, 80, 16), (1, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 7, 7, 5, 256), (1, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0): ((),),
+        ('norm_bwd', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (5, 1, 16)), (1, 1, 1), 0): ((),),
+        ('norm_bwd', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (5, 1, 128)), (1, 1, 1), 0): ((),),
+        ('norm_bwd', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (5, 1, 64)), (1, 1, 1), 0): ((),),
+        ('norm_bwd', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (5, 1, 32)), (1, 1, 1), 0): ((), ('partial',)),
+        ('norm_bwd', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (5, 1, 256)), (1, 1, 1), 0): ((), ('chan_scale',)),
+        ('norm_bwd_slabs', ((1, 14, 14, 10, 128), (4, 1, 14, 14, 10, 128), (5, 1, 128)), (4, 1, 1), 0): (('accumulate',),),
+        ('norm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1, 1), 0): (('chan_scale', 'partial', 'stats_only'), ('residual',)),
+        ('norm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1, 1), 0): ((), ('chan_scale',)),
+        ('norm_fwd_slabs', ((4, 1, 14, 14, 10, 128), (128,), (128,)), (4, 1, 1), 0): ((),),
+        ('pw16_bwd_norm_bwd', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1), 0): (('chan_scale', 'accumulate', 'norm_accumulate'),),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1, 2), 0): (('chan_scale',),),
+        ('up_dgrad', ((1, 112, 112, 80, 16), (4096,)), (32,), 1): ((),),
+        ('up_dgrad', ((1, 14, 14, 10, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((1, 28, 28, 20, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((1, 56, 56, 40, 32), (16384,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('mixloss_fwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): ((),),
+        ('mixloss_bwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): (('g_dev',),),
+    },
+    "pancreas_pre": {
+        ('conv3_c1_norm_bwd_wgrad', ((1, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0): (('dw_accumulate',),),
+        ('conv3_c1_norm_fwd', ((1, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 1, 1), 0): ((),),
+        ('down_dgrad', ((1, 12, 12, 12, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 24, 24, 24, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 48, 48, 48, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 6, 6, 6, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_fwd', ((1, 12, 12, 12, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((1, 24, 24, 24, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((1, 48, 48, 48, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((1, 96, 96, 96, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('k2_wgrad', ((1, 12, 12, 12, 128), (1, 24, 24, 24, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 12, 12, 12, 128), (1, 6, 6, 6, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 24, 24, 24, 64), (1, 12, 12, 12, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 24, 24, 24, 64), (1, 48, 48, 48, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 48, 48, 48, 32), (1, 24, 24, 24, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 48, 48, 48, 32), (1, 96, 96, 96, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 6, 6, 6, 256), (1, 12, 12, 12, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 96, 96, 96, 16), (1, 48, 48, 48, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 96, 96, 96, 1), (1, 96, 96, 96, 1)), (), 0): ((),),
+        ('norm_bwd', ((1, 12, 12, 12, 128), (1, 12, 12, 12, 128), (5, 1, 128)), (1, 1, 0), 0): ((),),
+        ('norm_bwd', ((1, 24, 24, 24, 64), (1, 24, 24, 24, 64), (5, 1, 64)), (1, 1, 0), 0): ((),),
+        ('norm_bwd', ((1, 48, 48, 48, 32), (1, 48, 48, 48, 32), (5, 1, 32)), (1, 1, 0), 0): ((), ('partial',)),
+        ('norm_bwd', ((1, 6, 6, 6, 256), (1, 6, 6, 6, 256), (5, 1, 256)), (1, 1, 0), 0): ((),),
+        ('norm_bwd', ((1, 96, 96, 96, 16), (1, 96, 96, 96, 16), (5, 1, 16)), (1, 1, 0), 0): ((),),
+        ('norm_bwd_slabs', ((1, 12, 12, 12, 128), (4, 1, 12, 12, 12, 128), (5, 1, 128)), (4, 1, 1), 0): ((),),
+        ('norm_fwd', ((1, 12, 12, 12, 128),), (1, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((1, 24, 24, 24, 64),), (1, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((1, 48, 48, 48, 32),), (1, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((1, 6, 6, 6, 256),), (1, 1), 0): ((),),
+        ('norm_fwd', ((1, 96, 96, 96, 16),), (1, 1), 0): (('partial', 'stats_only'), ('residual',)),
+        ('norm_fwd_slabs', ((4, 1, 12, 12, 12, 128), (128,)), (4, 1, 1), 0): ((),),
+        ('pw16_bwd_norm_bwd', ((1, 96, 96, 96, 16), (5, 1, 16), (1, 96, 96, 96, 2)), (1, 1), 0): (('accumulate',),),
+        ('pw16_fwd_norm', ((1, 96, 96, 96, 16), (5, 1, 16), (2, 16, 1, 1, 1)), (1, 1, 2), 0): ((),),
+        ('up_dgrad', ((1, 12, 12, 12, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((1, 24, 24, 24, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((1, 48, 48, 48, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((1, 96, 96, 96, 16), (4096,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 12, 12, 12, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 24, 24, 24, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 48, 48, 48, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_fwd', ((1, 6, 6, 6, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('mixloss_fwd', ((1, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): ((),),
+        ('mixloss_bwd', ((1, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): (('g_dev',),),
+    },
+    "acdc_pre": {
+        ('conv3_c1_norm_bwd_wgrad', ((6, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 1, 2), 0): (('elem_mask', 'accumulate', 'dw_accumulate'),),
+        ('conv3_c1_norm_fwd', ((6, 1, 256, 256, 1), (16, 1, 3, 3), (16,)), (1, 1, 2), 0): (('elem_mask',),),
+        ('k2_wgrad', ((6, 1, 128, 128, 32), (6, 1, 128, 128, 16), (16, 32, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((6, 1, 16, 16, 256), (6, 1, 16, 16, 128), (128, 256, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((6, 1, 32, 32, 128), (6, 1, 32, 32, 64), (64, 128, 1, 1)), (2,), 1): (('accumulate',),),
+        ('k2_wgrad', ((6, 1, 64, 64, 64), (6, 1, 64, 64, 32), (32, 64, 1, 1)), (2,), 1): (('accumulate',),),
+        ('mix_box', ((6, 1, 256, 256, 1), (6, 1, 256, 256, 1)), (), 0): ((),),
+        ('norm_bwd', ((6, 1, 128, 128, 32), (6, 1, 128, 128, 32), (5, 1, 32)), (1, 2, 1), 0): ((), ('elem_mask',), ('partial',)),
+        ('norm_bwd', ((6, 1, 16, 16, 256), (6, 1, 16, 16, 256), (5, 1, 256)), (1, 2, 1), 0): ((),),
+        ('norm_bwd', ((6, 1, 256, 256, 16), (6, 1, 256, 256, 16), (5, 1, 16)), (1, 2, 1), 0): ((),),
+        ('norm_bwd', ((6, 1, 32, 32, 128), (6, 1, 32, 32, 128), (5, 1, 128)), (1, 2, 1), 0): ((), ('elem_mask',)),
+        ('norm_bwd', ((6, 1, 64, 64, 64), (6, 1, 64, 64, 64), (5, 1, 64)), (1, 2, 1), 0): ((), ('elem_mask',)),
+        ('norm_bwd_slabs', ((6, 1, 16, 16, 256), (4, 6, 1, 16, 16, 256), (5, 1, 256)), (4, 1, 2), 0): (('elem_mask', 'accumulate'),),
+        ('norm_fwd', ((6, 1, 128, 128, 32), (32,), (32,)), (1, 2), 0): (('elem_mask', 'partial'), ('partial',), ('partial', 'out_slab')),
+        ('norm_fwd', ((6, 1, 256, 256, 16), (16,), (16,)), (1, 2), 0): (('partial',), ('partial', 'out_slab')),
+        ('norm_fwd', ((6, 1, 32, 32, 128), (128,), (128,)), (1, 2), 0): ((), ('elem_mask',), ('out_slab',)),
+        ('norm_fwd', ((6, 1, 64, 64, 64), (64,), (64,)), (1, 2), 0): (('elem_mask', 'partial'), ('partial',), ('partial', 'out_slab')),
+        ('norm_fwd_slabs', ((4, 6, 1, 16, 16, 256), (256,), (256,)), (4, 1, 2), 0): ((), ('elem_mask',)),
+        ('pw_fwd', ((6, 1, 128, 128, 16), (512,)), (32,), 0): ((),),
+        ('pw_fwd', ((6, 1, 128, 128, 32), (512,), (16,)), (16,), 1): ((),),
+        ('pw_fwd', ((6, 1, 16, 16, 128), (32768,)), (256,), 0): ((),),
+        ('pw_fwd', ((6, 1, 16, 16, 256), (32768,), (128,)), (128,), 1): ((),),
+        ('pw_fwd', ((6, 1, 32, 32, 128), (8192,), (64,)), (64,), 1): ((),),
+        ('pw_fwd', ((6, 1, 32, 32, 64), (8192,)), (128,), 0): ((),),
+        ('pw_fwd', ((6, 1, 64, 64, 32), (2048,)), (64,), 0): ((),),
+        ('pw_fwd', ((6, 1, 64, 64, 64), (2048,), (32,)), (32,), 1): ((),),
+        ('mixloss_fwd', ((6, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0): ((),),
+        ('mixloss_bwd', ((6, 1, 256, 256, 4), (6, 1, 256, 256), (6, 1, 256, 256)), (1,), 0): (('g_dev',),),
+    },
+    "la_val": {
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 0): ((),),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 0): ((),),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 0): ((),),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 0): ((),),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 0): ((),),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 0): ((),),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 0): ((),),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 0): ((),),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 0): ((),),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 0): ((),),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 0): ((),),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 0): ((),),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 0): ((),),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 0): ((),),
+        ('up_fwd', ((4, 56, 56, 40, 32), (4096,), (16,)), (16,), 0): ((),),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 0): ((),),
+        ('norm_eval', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((),),
+        ('norm_eval', ((4, 112, 112, 80, 16), (16,), (16,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((4, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((4, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((4, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('residual',)),
+        ('norm_eval', ((4, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((),),
+    },
+    "pancreas_val": {
+        ('down_fwd', ((1, 12, 12, 12, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((1, 24, 24, 24, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((1, 48, 48, 48, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((1, 96, 96, 96, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_fwd', ((4, 12, 12, 12, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((4, 24, 24, 24, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((4, 48, 48, 48, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((4, 96, 96, 96, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('norm_fwd', ((1, 12, 12, 12, 128),), (1, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((1, 24, 24, 24, 64),), (1, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((1, 48, 48, 48, 32),), (1, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((1, 6, 6, 6, 256),), (1, 1), 0): ((),),
+        ('norm_fwd', ((1, 96, 96, 96, 16),), (1, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((4, 12, 12, 12, 128),), (4, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((4, 24, 24, 24, 64),), (4, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((4, 48, 48, 48, 32),), (4, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((4, 6, 6, 6, 256),), (4, 1), 0): ((),),
+        ('norm_fwd', ((4, 96, 96, 96, 16),), (4, 1), 0): ((), ('partial',), ('residual',)),
+        ('up_fwd', ((1, 12, 12, 12, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 24, 24, 24, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 48, 48, 48, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_fwd', ((1, 6, 6, 6, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((4, 12, 12, 12, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((4, 24, 24, 24, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((4, 48, 48, 48, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_fwd', ((4, 6, 6, 6, 256), (262144,), (128,)), (128,), 1): ((),),
+    },
+    "acdc_val": {
+        ('pw_fwd', ((1, 1, 128, 128, 32), (512,), (16,)), (16,), 0): ((),),
+        ('pw_fwd', ((1, 1, 16, 16, 256), (32768,), (128,)), (128,), 0): ((),),
+        ('pw_fwd', ((1, 1, 32, 32, 128), (8192,), (64,)), (64,), 0): ((),),
+        ('pw_fwd', ((1, 1, 64, 64, 64), (2048,), (32,)), (32,), 0): ((),),
+        ('pw_fwd', ((16, 1, 128, 128, 32), (512,), (16,)), (16,), 0): ((),),
+        ('pw_fwd', ((16, 1, 16, 16, 256), (32768,), (128,)), (128,), 0): ((),),
+        ('pw_fwd', ((16, 1, 32, 32, 128), (8192,), (64,)), (64,), 0): ((),),
+        ('pw_fwd', ((16, 1, 64, 64, 64), (2048,), (32,)), (32,), 0): ((),),
+        ('norm_eval', ((1, 1, 128, 128, 32), (32,), (32,)), (2,), 0): ((),),
+        ('norm_eval', ((1, 1, 16, 16, 256), (256,), (256,)), (2,), 0): ((),),
+        ('norm_eval', ((1, 1, 256, 256, 16), (16,), (16,)), (2,), 0): ((),),
+        ('norm_eval', ((1, 1, 32, 32, 128), (128,), (128,)), (2,), 0): ((),),
+        ('norm_eval', ((1, 1, 64, 64, 64), (64,), (64,)), (2,), 0): ((),),
+        ('norm_eval', ((16, 1, 128, 128, 32), (32,), (32,)), (2,), 0): ((),),
+        ('norm_eval', ((16, 1, 16, 16, 256), (256,), (256,)), (2,), 0): ((),),
+        ('norm_eval', ((16, 1, 256, 256, 16), (16,), (16,)), (2,), 0): ((),),
+        ('norm_eval', ((16, 1, 32, 32, 128), (128,), (128,)), (2,), 0): ((),),
+        ('norm_eval', ((16, 1, 64, 64, 64), (64,), (64,)), (2,), 0): ((),),
+    },
+    "la8": {
+        ('conv3_c1_norm_bwd_wgrad', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): (('accumulate', 'dw_accumulate'),),
+        ('conv3_c1_norm_fwd', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2, 1), 0): ((),),
+        ('down_dgrad', ((4, 14, 14, 10, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((4, 28, 28, 20, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((4, 56, 56, 40, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((4, 7, 7, 5, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('k2_fwd_stats', ((4, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 2), 1): ((),),
+        ('k2_wgrad', ((4, 112, 112, 80, 16), (4, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 14, 14, 10, 128), (4, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 14, 14, 10, 128), (4, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 28, 28, 20, 64), (4, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 28, 28, 20, 64), (4, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 56, 56, 40, 32), (4, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 56, 56, 40, 32), (4, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((4, 7, 7, 5, 256), (4, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('mix_box', ((2, 112, 112, 80, 1), (2, 112, 112, 80, 1)), (), 0): (('out',),),
+        ('mixloss_pair_bwd', ((4, 112, 112, 80, 2), (2, 112, 112, 80), (2, 112, 112, 80)), (0,), 0): (('out', 'g_dev'),),
+        ('mixloss_pair_fwd', ((4, 112, 112, 80, 2), (2, 112, 112, 80), (2, 112, 112, 80)), (0,), 0): ((),),
+        ('norm_bwd', ((4, 112, 112, 80, 16), (4, 112, 112, 80, 16), (5, 2, 16)), (2, 1, 1), 0): ((),),
+        ('norm_bwd', ((4, 14, 14, 10, 128), (4, 14, 14, 10, 128), (5, 2, 128)), (2, 1, 1), 0): ((),),
+        ('norm_bwd', ((4, 28, 28, 20, 64), (4, 28, 28, 20, 64), (5, 2, 64)), (2, 1, 1), 0): ((), ('partial',)),
+        ('norm_bwd', ((4, 56, 56, 40, 32), (4, 56, 56, 40, 32), (5, 2, 32)), (2, 1, 1), 0): ((), ('partial',)),
+        ('norm_bwd', ((4, 7, 7, 5, 256), (4, 7, 7, 5, 256), (5, 2, 256)), (2, 1, 1), 0): (('chan_scale',),),
+        ('norm_bwd_slabs', ((4, 14, 14, 10, 128), (2, 4, 14, 14, 10, 128), (5, 2, 128)), (2, 2, 1), 0): (('accumulate',),),
+        ('norm_bwd_slabs', ((4, 7, 7, 5, 256), (8, 4, 7, 7, 5, 256), (5, 2, 256)), (8, 2, 1), 0): (('accumulate',),),
+        ('norm_fwd', ((4, 112, 112, 80, 16), (16,), (16,)), (2, 1), 0): (('chan_scale', 'partial', 'stats_only'), ('partial', 'residual')),
+        ('norm_fwd', ((4, 14, 14, 10, 128), (128,), (128,)), (2, 1), 0): ((), ('residual',)),
+        ('norm_fwd', ((4, 28, 28, 20, 64), (64,), (64,)), (2, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((4, 56, 56, 40, 32), (32,), (32,)), (2, 1), 0): ((), ('partial',), ('residual',)),
+        ('norm_fwd', ((4, 7, 7, 5, 256), (256,), (256,)), (2, 1), 0): ((),),
+        ('norm_fwd_slabs', ((2, 4, 14, 14, 10, 128), (128,), (128,)), (2, 2, 1), 0): ((),),
+        ('norm_fwd_slabs', ((8, 4, 7, 7, 5, 256), (256,), (256,)), (8, 2, 1), 0): ((), ('chan_scale',)),
+        ('pw16_bwd_norm_bwd', ((4, 112, 112, 80, 16), (5, 2, 16), (4, 16)), (2, 1), 0): (('chan_scale', 'accumulate', 'norm_accumulate'),),
+        ('pw16_fwd_norm', ((4, 112, 112, 80, 16), (5, 2, 16), (4, 16)), (2, 1, 2), 0): (('chan_scale',),),
+        ('up_dgrad', ((4, 112, 112, 80, 16), (4096,)), (32,), 1): ((),),
+        ('up_dgrad', ((4, 14, 14, 10, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((4, 28, 28, 20, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((4, 56, 56, 40, 32), (16384,)), (64,), 1): ((),),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+    },
 }
 
 
@@ -1845,4 +2964,6 @@ def run_row(ops, dev, wl, key, g, table_key=None):
         return fn(ops, dev, key, g, variants_of(wl, table_key or key))
     if fn is drive_pack_many:
         return fn(ops, dev, key, g, wl)
+    if fn is drive_conv:
+        return fn(ops, dev, key, g, step_groups(wl), stats_fused(wl, table_key or key) if key[0] == "conv3_fwd_stats" else True)
     return fn(ops, dev, key, g)

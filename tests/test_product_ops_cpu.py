@@ -64,12 +64,13 @@ def _reduced_rows():
     return rows
 
 
-# the LA rows run in the default CPU suite; the pancreas / ACDC rows (same drivers, other shapes) with BCP_EXTENDED=1.
+# the LA rows (self-training, pre-training, validation) run in the default CPU suite; the pancreas / ACDC / batch-8 rows (same drivers,
+# other shapes) with BCP_EXTENDED=1.
 # At the reduced shapes the dispatch may differ from the in-step one: a conv3_fwd_raw row falls back to conv3_fwd where the shape is
 # not served raw, and where a conv leaves no fused statistics (rows == 0) the fwd_stats / dgrad_bwdstats rows and the norm rows' "partial"
 # epilogue run without them.  These rows check the drivers and references on the simulator; the route itself is asserted on the device
 # (tests/test_gpu_product_ops.py: each row must launch its key, and the drivers require the fused routes there).
-@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] == "la" else pytest.mark.extended) for r in _reduced_rows()],
+@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] in ("la", "la_pre", "la_val") else pytest.mark.extended) for r in _reduced_rows()],
                          ids=[P.row_id(r[0], r[1]) for r in _reduced_rows()])
 def test_product_op_reduced_on_simulator(emu_ops, wl, key, rkey):  # noqa: F811
     g = torch.Generator().manual_seed(5)
@@ -142,14 +143,97 @@ def test_mixloss_closed_form_matches_oracle_autograd(flavour, ls):
         assert bool((cond >= gr.abs() * (1 - 1e-12)).all())
 
 
+UNDRIVEN = {}        # {op: reason} -- ops of the table that are left without a driver on purpose (none)
+
+
 def test_every_step_op_has_a_driver():
-    """a new op in a step cannot go undriven: every op of STEP_KEYS has a driver, and the driven rows are the whole table plus the
-    keys only a statistics-only norm call uses"""
-    assert {k[0] for _, k in P.table_rows()} <= set(P.DRIVERS)
+    """a new op in a step, a pre-training step or a validation pass cannot go undriven: every op of STEP_KEYS has a driver, every table
+    row is driven under its own workload or is the repeat of a row driven under an earlier one (same key, same flags), and the only
+    rows outside the table are the keys a statistics-only norm call uses"""
+    assert sorted(P.STEP_KEYS) == sorted(["la", "pancreas", "acdc", "la_pre", "pancreas_pre", "acdc_pre", "la_val", "pancreas_val", "acdc_val", "la8"])
+    assert {k[0] for _, k in P.table_rows()} - set(UNDRIVEN) <= set(P.DRIVERS)
     rows = P.driven_rows()
-    assert len(P.table_rows()) == 223 and set(P.table_rows()) <= set(rows)
+    assert len(P.table_rows()) == 671 and len(set(rows)) == len(rows)
+    first = [(wl, k) for wl, k in P.table_rows() if wl in ("la", "pancreas", "acdc")]
+    assert len(first) == 223 and set(first) <= set(rows)                      # (the self-training table is driven as before)
+    driven = {P._row_ident(wl, k) for wl, k in rows}
+    assert all(P._row_ident(wl, k) in driven for wl, k in P.table_rows() if k[0] not in UNDRIVEN)
     extra = [k for _, k in rows if (_, k) not in set(P.table_rows())]
     assert all(k[0] == "norm_fwd" for k in extra), extra
+    for op in ("norm_eval", "sw_accumulate", "sw_finish", "overlap_counts", "plabel_argmax4", "mixloss_fwd", "mixloss_bwd", "conv3_c1_fwd", "pw16_fwd",
+               "copy_channels"):
+        assert any(k[0] == op for _, k in rows), op
+
+
+def test_norm_eval_reference_matches_torch():
+    """norm_eval_ref64 against F.batch_norm(training=False) + activation + residual in fp64; its cond bounds the result"""
+    import numpy as np
+    F = torch.nn.functional
+    g = torch.Generator().manual_seed(14)
+    y = torch.randn(2, 3, 4, 5, 8, generator=g, dtype=torch.float64) * 3 + 1
+    gam, bet = torch.rand(8, generator=g, dtype=torch.float64) + 0.5, torch.rand(8, generator=g, dtype=torch.float64) - 0.5
+    rm, rv = torch.randn(8, generator=g, dtype=torch.float64), torch.pow(10.0, torch.rand(8, generator=g, dtype=torch.float64) * 4 - 2)
+    res = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    bn = F.batch_norm(y.permute(0, 4, 1, 2, 3), rm, rv, gam, bet, training=False, eps=float(np.float32(1e-5))).permute(0, 2, 3, 4, 1)
+    for act, fn in ((1, torch.relu), (2, lambda t: F.leaky_relu(t, 0.01))):
+        for r in (None, res):
+            a, z, cond, zcond = P.norm_eval_ref64(y, gam, bet, rm, rv, act, r)
+            assert torch.allclose(z, bn, rtol=1e-12, atol=1e-12)
+            assert torch.allclose(a, fn(bn) + (0 if r is None else r), rtol=1e-12, atol=1e-12)
+            assert bool((cond >= a.abs() * (1 - 1e-12)).all()) and bool((zcond >= z.abs() * (1 - 1e-12)).all())
+
+
+def test_sliding_window_reference_matches_a_plain_loop():
+    """sw_origins against the clamped grid written out, sw_ref against a voxel-by-voxel Python loop (math.exp, fp64)"""
+    import math
+    vol, patch = (5, 4, 7), (3, 4, 4)
+    org = P.sw_origins(vol, patch, 2, 2)
+    assert org == [(0, 0, 0), (0, 0, 2), (0, 0, 3), (2, 0, 0), (2, 0, 2), (2, 0, 3)]           # (z: 0, 2, then 4 clamped to 7 - 4)
+    assert P.sw_origins((112, 112, 96), (112, 112, 80)) == [(0, 0, z) for z in (0, 4, 8, 12, 16)]
+    assert len(P.sw_origins((96, 96, 112), (96, 96, 96))) == 5 and len(P.sw_origins((112, 112, 80), (112, 112, 80))) == 1
+    g = torch.Generator().manual_seed(15)
+    for C in (2, 4):
+        logits = P._sw_logits(g, vol, patch, C, org)
+        for cls in range(C):
+            score = [[[0.0] * vol[2] for _ in range(vol[1])] for _ in range(vol[0])]
+            cnt = [[[0] * vol[2] for _ in range(vol[1])] for _ in range(vol[0])]
+            for lg, (x0, y0, z0) in zip(logits, org):
+                for i in range(patch[0]):
+                    for j in range(patch[1]):
+                        for k in range(patch[2]):
+                            e = [math.exp(float(v)) for v in lg[i, j, k]]
+                            score[x0 + i][y0 + j][z0 + k] += e[cls] / sum(e)
+                            cnt[x0 + i][y0 + j][z0 + k] += 1
+            ref, rc = P.sw_ref(logits, org, vol, cls)
+            assert torch.equal(rc, torch.tensor(cnt))
+            assert torch.allclose(ref, torch.tensor(score, dtype=torch.float64) / torch.tensor(cnt, dtype=torch.float64), rtol=1e-13, atol=0)
+
+
+@pytest.mark.parametrize("flavour,ls", [(0, (2, 6, 8, 8, 2)), (1, (3, 1, 12, 12, 4))], ids=["la", "acdc"])
+def test_mixloss_single_closed_form_matches_oracle_autograd(flavour, ls):
+    """mixloss64 as the pre-training steps use it -- LA: one label map, the all-zero box, weights (1, 0); ACDC: two label maps, a real
+    box, weights (1, 1) -- against fp64 autograd of the oracle's mix_loss_la / mix_loss_acdc: <= 1e-12"""
+    import bcp_oracle as O
+    g = torch.Generator().manual_seed(4)
+    sp, C, N = ls[1:4], ls[-1], ls[0]
+    for box6, w, same in ([((0,) * 6, (1.0, 0.0), True)] if flavour == 0 else [(b, (1.0, 1.0), False) for b in P._boxes(sp, g)]):
+        logits, labs = P._loss_inputs(g, (2 * N,) + tuple(ls[1:]), C)
+        logits = logits[:N]
+        img_l, patch_l = labs[0][0], labs[0][0] if same else labs[0][1]
+        o3, gr, cond = P.mixloss64(logits, img_l, patch_l, box6, flavour, w)
+        L = logits.double().requires_grad_(True)
+        nc = L.permute(0, 4, 1, 2, 3)
+        mask = (~P._in_box(sp, box6)).double().unsqueeze(0).expand(N, *sp)
+        if flavour == 0:
+            loss = O.mix_loss_la(nc, img_l, patch_l, mask, l_weight=w[0], u_weight=w[1])
+            d = abs(float(loss.detach()) - float(o3[0]))
+        else:
+            dice, ce = O.mix_loss_acdc(nc[:, :, 0], img_l[:, 0], patch_l[:, 0], mask[:, 0], l_weight=w[0], u_weight=w[1])
+            loss = (dice + ce) / 2
+            d = max(abs(float(dice.detach()) - float(o3[0])), abs(float(ce.detach()) - float(o3[1])))
+        loss.backward()
+        assert d <= 1e-12, (box6, d)
+        assert float((L.grad - gr).abs().max()) <= 1e-12 and P.elementwise_ratio(L.grad, gr, cond)[0] <= 1e-12, box6
 
 
 # -------------------------------------------------------------------------------------------------- would the drivers notice?
@@ -214,11 +298,65 @@ def _ragged_tail(t):
     return rows[(rows.shape[0] - 1) // 64 * 64:]
 
 
-def _la_row(op, pick=0):
-    return [(wl, k) for wl, k in P.table_rows() if wl == "la" and k[0] == op][pick]
+def _la_row(op, pick=0, wl="la"):
+    return [(w, k) for w, k in P.table_rows() if w == wl and k[0] == op][pick]
 
 
-# case: (op of the LA row driven, op corrupted, corruption[, which of the op's LA rows]).  What the older comparators say of the same
+def _smallest_variance_without_eps(a):
+    rv = a[4].clone()
+    rv[int(torch.argmin(rv))] -= 1e-5                # one channel: 1 / sqrt(rv) instead of 1 / sqrt(rv + eps)
+    a[4] = rv
+    return a
+
+
+def _sw_last_origin_shifted(c, orig, lg, score, cnt, origin, cls=1):
+    """the clamped last origin one voxel off along z (towards the volume: the run stays inside the maps)"""
+    s0, c0 = score.clone(), cnt.clone()
+    orig(lg, s0, c0, origin, cls=cls)
+    bad = (origin[0], origin[1], origin[2] - 1) if origin[2] + lg.shape[2] == score.shape[2] and origin[2] > 0 else origin
+    orig(lg, score, cnt, bad, cls=cls)
+    if bad != origin:
+        c.pairs.append((s0, score.clone()))
+
+
+def _sw_visit_counted_twice(c, orig, lg, score, cnt, origin, cls=1):
+    orig(lg, score, cnt, origin, cls=cls)
+    if tuple(origin) == (0, 0, 0):
+        clean = cnt.clone()
+        cnt[:lg.shape[0], :lg.shape[1], :lg.shape[2]] += 1
+        c.pairs.append((clean, cnt.clone()))
+
+
+def _sw_finish_ge(c, orig, score, cnt, thres=0.5):
+    lab = orig(score, cnt, thres)
+    bad = (score >= thres).to(torch.uint8)
+    c.pairs.append((lab.float(), bad.float()))
+    return bad
+
+
+def _overlap_tail_dropped(c, orig, pred, gt, cls=0):
+    n = pred.numel() // 256 * 256
+    clean = orig(pred, gt, cls)
+    bad = orig(pred.reshape(-1)[:n].contiguous(), gt.reshape(-1)[:n].contiguous(), cls) if n else torch.zeros_like(clean)
+    c.pairs.append((clean.float(), bad.float()))
+    return bad
+
+
+def _zero_box_as_full_volume(a):
+    if not any(a[3]):
+        a[3] = (0, 0, 0) + tuple(a[0].shape[1:4])
+    return a
+
+
+def _stale_amax(a):
+    from bcp_amd import hip_ops as H
+    x = a[0].clone()
+    x._bcp_amax = H.amax_slots(float(x.abs().max()) / 4096, x.device)        # a |max| left over from a far smaller tensor
+    a[0] = x
+    return a
+
+
+# case: (op of the LA row driven, op corrupted, corruption[, which of the op's rows[, its workload[, the divisor of the reduced shape]]]).  What the older comparators say of the same
 # outputs at these reduced shapes (the test prints it): kernel_checks.close(), scaled by the tensor's largest element, accepts only the
 # conv pack's changed word; a rel-L2 1e-4 test accepts the scaled first-layer channel (9.6e-5) and both pack words, and is within 4x of
 # accepting every 1 + 2^-10 / 2^-12 scaling (1.2e-4 .. 6.7e-4).
@@ -238,6 +376,15 @@ SENSITIVITY = {
     "head-gradient-channel": ("pw16_bwd_norm_bwd", "pw16_bwd_norm_bwd", _scaled(lambda t: t[..., 3], 1 + 2.0 ** -10)),
     "pack-one-word": ("conv3_pack_many", "conv3_pack", _scaled(lambda t: t[7:8], 1 + 2.0 ** -10)),
     "k2-pack-one-word": ("k2_pack_many", "k2_pack", _scaled(lambda t: t[7:8], 1 + 2.0 ** -10)),
+    # the pre-training and validation rows (the LA workloads la_pre / la_val)
+    "norm-eval-variance-without-eps": ("norm_eval", "norm_eval", _rerun(_smallest_variance_without_eps), 0, "la_val"),
+    "sw-last-origin-off-by-one": ("sw_accumulate", "sw_accumulate", _sw_last_origin_shifted, 0, "la_val"),
+    "sw-visit-counted-twice": ("sw_accumulate", "sw_accumulate", _sw_visit_counted_twice, 0, "la_val"),
+    "sw-finish-greater-or-equal": ("sw_finish", "sw_finish", _sw_finish_ge, 0, "la_val"),
+    "overlap-tail-dropped": ("overlap_counts", "overlap_counts", _overlap_tail_dropped, 0, "la_val"),
+    "mixloss-zero-box-as-full-volume": ("mixloss_fwd", "mixloss_fwd", _rerun(_zero_box_as_full_volume), 0, "la_pre"),
+    # (the row 1 x 28 x 28 x 20 x 64 at half its extents: the reduced shape at which the simulator's library has a two-plane fp16 instance)
+    "conv-stale-amax": ("conv3_fwd", "conv3_fwd", _rerun(_stale_amax), 2, "la_val", 2),
 }
 
 
@@ -249,8 +396,8 @@ def test_driver_rejects_corruption(emu_ops, case):  # noqa: F811
     note says whether kernel_checks.close() (max-scaled) or a rel-L2 1e-4 test would have accepted the same output."""
     import kernel_checks as K
     row_op, bad_op, fn, *pick = SENSITIVITY[case]
-    wl, key = _la_row(row_op, *pick)
-    rkey = P.reduce_key(key)
+    wl, key = _la_row(row_op, *pick[:2])
+    rkey = P.reduce_key(key, *pick[2:])
     g = torch.Generator().manual_seed(5)
     P.run_row(emu_ops, torch.device("cpu"), wl, rkey, g, table_key=key)                  # the clean op passes
     bad = _Corrupt(emu_ops, bad_op, fn)
