@@ -40,6 +40,9 @@ for _name, _type, _default, _help in _BUILD_FLAGS:
     parser.add_argument("--" + _name, type=_type, default=_default, help=_help)
 parser.add_argument("--augment", action="store_true",
                     help="raw-size slices + the device-side RandomGenerator (rot90 / flip / rotate + zoom, dataloaders/dataset.py)")
+parser.add_argument("--val_surface", action="store_true",
+                    help="validation also computes medpy's hd95 per class on the device (utils/surface.py) and logs its mean; "
+                         "checkpoints are still chosen by Dice, as in the reference")
 parser.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "contact"),
                     help="the copy-paste region: box = one 2/3-side box (generate_mask, the reference's command line), random = 9 small boxes "
                          "(ACDC_BCP_train.py:142 random_mask), contact = one full-width band (:156 contact_mask)")
@@ -92,12 +95,13 @@ def _val_set(args, device):
     return out
 
 
-def _validate(model, val_set, num_classes):
-    """per-class (dice, hd95) averaged over the validation volumes -> mean Dice (:274-283)"""
+def _validate(model, val_set, num_classes, surface=False):
+    """per-class (dice, hd95) averaged over the validation volumes -> (mean Dice, mean hd95) (:274-283); hd95 is nan unless `surface`"""
     total = 0.0
     for image, label in val_set:
-        total = total + np.array(val_2d.test_single_volume(image, label, model, classes=num_classes), dtype=np.float64)
-    return float(np.mean(total / max(len(val_set), 1), axis=0)[0])
+        total = total + np.array(val_2d.test_single_volume(image, label, model, classes=num_classes, surface=surface), dtype=np.float64)
+    mean = np.mean(total / max(len(val_set), 1), axis=0)
+    return float(mean[0]), float(mean[1])
 
 
 class _BestModel:
@@ -120,12 +124,15 @@ class _BestModel:
         a = self.args
         if a.val_every <= 0 or iter_num % a.val_every:
             return
-        performance = _validate(model, self.val_set, a.num_classes)
+        performance, mean_hd95 = _validate(model, self.val_set, a.num_classes, surface=a.val_surface)
         if performance > self.best:
             self.best = performance
             self._write(model, optimizer, "iter_{}_dice_{}.pth".format(iter_num, round(self.best, 4)))
             self._write(model, optimizer, "{}_best_model.pth".format(a.model))
-        logging.info("iteration %d : mean_dice : %f" % (iter_num, performance))
+        if a.val_surface:
+            logging.info("iteration %d : mean_dice : %f mean_hd95 : %f" % (iter_num, performance, mean_hd95))
+        else:
+            logging.info("iteration %d : mean_dice : %f" % (iter_num, performance))
 
     def finish(self, model, optimizer):
         if self.best == 0.0:

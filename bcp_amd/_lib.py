@@ -14,7 +14,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libbcp_hip.so")
 
-ABI_VERSION = 512      # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
+ABI_VERSION = 513     # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
 
 P = C.c_void_p
 I = C.c_int
@@ -128,6 +128,9 @@ _SIGS = {
     "bcp_sw_accumulate": (I, [P, P, P, I, I, I, I, I, I, I, I, I, I, I, P]),
     "bcp_sw_finish": (I, [P, P, P, L, F, P]),
     "bcp_overlap_counts": (I, [P, P, L, I, P, P]),
+    "bcp_surface_border": (I, [P, I, I, I, I, P, P, P]),
+    "bcp_edt_sq": (I, [P, I, I, I, P, P, P]),
+    "bcp_surface_hist": (I, [P, P, I, I, I, P, I, P]),
     "bcp_crop_rotflip": (I, [P, P, I, I, I, I, I, I, I, I, I, I, I, I, I, I, I, P]),
     "bcp_acdc_augment": (I, [P, P, I, I, I, I, I, I, P, I, I, P]),
     "bcp_cast": (I, [P, P, L, I, P]),

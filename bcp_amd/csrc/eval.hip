@@ -130,6 +130,125 @@ extern "C" int bcp_overlap_counts(const uint8_t* pred, const uint8_t* gt, long l
 }
 
 // ------------------------------------------------------------------------------------------------
+// Surface distances (medpy.metric.binary.hd95 / asd as called by utils/test_3d_patch.py:269-273, pancreas/test_util.py:20-24,
+// utils/val_2d.py:9-17, test_ACDC.py:26-33: unit voxel spacing, connectivity 1) in integers: the border map of an object, the exact
+// SQUARED Euclidean distance to the nearest border voxel of the other object, and the histogram of those squared distances over the
+// border voxels.  The host finishes the percentile and the mean from two histograms (bcp_amd/utils/surface.py).
+// ------------------------------------------------------------------------------------------------
+namespace bcp {
+
+// border[v] = sel(seg[v]) && some 6-neighbour is outside the volume or not selected  (m ^ binary_erosion(m, cross), border_value 0);
+// *count += number of border voxels
+__global__ __launch_bounds__(256) void k_surface_border(const uint8_t* __restrict__ seg, int D, int H, int W, int cls,
+                                                        uint8_t* __restrict__ border, unsigned long long* __restrict__ count) {
+  const long long hw = (long long)H * W, n = hw * D;
+  unsigned long long c = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W), h = (int)((i / W) % H), d = (int)(i / hw);
+    auto sel = [&](long long q) { return cls ? seg[q] == cls : seg[q] != 0; };
+    bool b = false;
+    if (sel(i)) {
+      b = d == 0 || d == D - 1 || h == 0 || h == H - 1 || w == 0 || w == W - 1;
+      if (!b) b = !(sel(i - hw) && sel(i + hw) && sel(i - W) && sel(i + W) && sel(i - 1) && sel(i + 1));
+    }
+    border[i] = b ? 1 : 0;
+    c += b;
+  }
+  c = wave_sum(c);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+
+// pass 1, along W: out[v] = (distance to the nearest site in v's W line)^2, BCP_EDT_NOSITE when the line has none
+__global__ __launch_bounds__(256) void k_edt_w(const uint8_t* __restrict__ sites, long long n, int W, int* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int w = (int)(i % W);
+    const uint8_t* line = sites + (i - w);
+    int best = BCP_EDT_NOSITE;
+    for (int r = 0; r < W; ++r) {            // outwards from w: the first hit is the nearest
+      if ((w - r >= 0 && line[w - r]) || (w + r < W && line[w + r])) { best = r * r; break; }
+    }
+    out[i] = best;
+  }
+}
+
+// passes 2 and 3, along an axis of L entries `inner` elements apart: out[i] = min_j (g[j] + (i - j)^2), brute force and exact.  The walk
+// goes outwards from i and stops at the first r with r^2 >= the best so far: no j further away can lower it.  Threads are along the
+// unit-stride axis, so every g[j] read is one coalesced row per wave (the re-reads come out of the L2).
+__global__ __launch_bounds__(256) void k_edt_line(const int* __restrict__ g, long long n, int L, long long inner, int* __restrict__ out) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int p = (int)((i / inner) % L);
+    const int* line = g + (i - (long long)p * inner);
+    int best = line[(long long)p * inner];
+    for (int r = 1; r < L; ++r) {
+      const int rr = r * r;
+      if (rr >= best) break;
+      if (p - r >= 0) { const int v = line[(long long)(p - r) * inner] + rr; best = v < best ? v : best; }
+      if (p + r < L) { const int v = line[(long long)(p + r) * inner] + rr; best = v < best ? v : best; }
+    }
+    out[i] = best;
+  }
+}
+
+// hist[d2_to[v]] += 1 for every v with border_from[v] != 0 (a value outside the bins -- an empty site map -- is not counted)
+__global__ __launch_bounds__(256) void k_surface_hist(const uint8_t* __restrict__ border_from, const int* __restrict__ d2_to, long long n,
+                                                      unsigned* __restrict__ hist, int nbins) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    if (border_from[i]) {
+      const int v = d2_to[i];
+      if (v >= 0 && v < nbins) atomicAdd(&hist[v], 1u);
+    }
+  }
+}
+
+}  // namespace bcp
+
+static inline bool surf_extent_ok(int D, int H, int W) { return D >= 1 && D <= 1024 && H >= 1 && H <= 1024 && W >= 1 && W <= 1024; }
+
+// count: device uint64, zeroed here
+extern "C" int bcp_surface_border(const uint8_t* seg, int D, int H, int W, int cls, uint8_t* border, unsigned long long* count, void* stream) {
+  BCP_REQUIRE(seg && border && count, "bcp_surface_border: null pointer");
+  BCP_REQUIRE(surf_extent_ok(D, H, W), "bcp_surface_border: extents %d x %d x %d outside 1..1024", D, H, W);
+  BCP_REQUIRE(cls >= 0 && cls < 256, "bcp_surface_border: cls=%d outside 0..255", cls);
+  const long long n = (long long)D * H * W;
+  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), (hipStream_t)stream) != hipSuccess) {
+    bcp::set_error("bcp_surface_border: clearing the count failed");
+    return BCP_ELAUNCH;
+  }
+  hipLaunchKernelGGL(k_surface_border, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, seg, D, H, W, cls, border, count);
+  BCP_CHECK_LAUNCH("bcp_surface_border");
+  return BCP_OK;
+}
+
+extern "C" int bcp_edt_sq(const uint8_t* sites, int D, int H, int W, int32_t* out, int32_t* scratch, void* stream) {
+  BCP_REQUIRE(sites && out && scratch, "bcp_edt_sq: null pointer");
+  BCP_REQUIRE(out != scratch, "bcp_edt_sq: out and scratch must be two volumes");
+  BCP_REQUIRE(surf_extent_ok(D, H, W), "bcp_edt_sq: extents %d x %d x %d outside 1..1024", D, H, W);
+  const long long n = (long long)D * H * W;
+  const int g = egrid(n);
+  hipLaunchKernelGGL(k_edt_w, dim3(g), dim3(256), 0, (hipStream_t)stream, sites, n, W, out);
+  hipLaunchKernelGGL(k_edt_line, dim3(g), dim3(256), 0, (hipStream_t)stream, (const int*)out, n, H, (long long)W, scratch);
+  hipLaunchKernelGGL(k_edt_line, dim3(g), dim3(256), 0, (hipStream_t)stream, (const int*)scratch, n, D, (long long)H * W, out);
+  BCP_CHECK_LAUNCH("bcp_edt_sq");
+  return BCP_OK;
+}
+
+// hist: device uint32[nbins], zeroed here
+extern "C" int bcp_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int D, int H, int W, unsigned* hist, int nbins, void* stream) {
+  BCP_REQUIRE(border_from && d2_to && hist, "bcp_surface_hist: null pointer");
+  BCP_REQUIRE(surf_extent_ok(D, H, W), "bcp_surface_hist: extents %d x %d x %d outside 1..1024", D, H, W);
+  const long long need = (long long)(D - 1) * (D - 1) + (long long)(H - 1) * (H - 1) + (long long)(W - 1) * (W - 1) + 1;
+  BCP_REQUIRE(nbins >= need, "bcp_surface_hist: %d bins, need at least %lld", nbins, need);
+  const long long n = (long long)D * H * W;
+  if (hipMemsetAsync(hist, 0, (size_t)nbins * sizeof(unsigned), (hipStream_t)stream) != hipSuccess) {
+    bcp::set_error("bcp_surface_hist: clearing the bins failed");
+    return BCP_ELAUNCH;
+  }
+  hipLaunchKernelGGL(k_surface_hist, dim3(egrid(n)), dim3(256), 0, (hipStream_t)stream, border_from, d2_to, n, hist, nbins);
+  BCP_CHECK_LAUNCH("bcp_surface_hist");
+  return BCP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Device-side input pipeline for LA: RandomRotFlip + RandomCrop (dataloaders/dataset.py:52-59, 173-214)
 // as ONE gather: dst[i][j][l] = pad(flip(rot90(src, k), axis))[w1+i][h1+j][d1+l], zero in the padding.
 // ------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ CAST_I64_U8, CAST_F32_U8, CAST_U8_F32, CAST_U8_I64 = range(4)
 
 
 AMAX_FLOATS, AMAX_STRIDE = 1024, 32      # csrc/common.h kAmaxFloats / kAmaxStride
+EDT_NOSITE = 1 << 30                     # include/bcp_hip.h BCP_EDT_NOSITE: Ops.edt_sq of a line / volume without a site
 
 
 def amax_slots(value, device):
@@ -449,6 +450,51 @@ class Ops:
         counts = torch.empty(3, dtype=torch.int64, device=pred.device)
         self.b.call("bcp_overlap_counts", _p(pred), _p(gt), pred.numel(), int(cls), _p(counts), self.stream(pred))
         return counts
+
+    def surface_border(self, seg, cls=0):
+        """seg: uint8 [D,H,W] -> (border uint8 [D,H,W], count int64[1] device tensor): the object's voxels (seg != 0, or == cls when
+        cls > 0) with a 6-neighbour outside the object or outside the volume (medpy's m ^ binary_erosion(m))"""
+        self._chk(seg)
+        if seg.dtype != torch.uint8 or seg.dim() != 3:
+            raise _lib.BcpError("surface_border: a uint8 [D,H,W] volume")
+        D, H, W = seg.shape
+        border = torch.empty_like(seg)
+        count = torch.empty(1, dtype=torch.int64, device=seg.device)
+        self.b.call("bcp_surface_border", _p(seg), D, H, W, int(cls), _p(border), _p(count), self.stream(seg))
+        return border, count
+
+    def edt_sq(self, sites, scratch=None):
+        """sites: uint8 [D,H,W] -> int32 [D,H,W]: exact squared Euclidean distance (voxels) to the nearest nonzero voxel of `sites`
+        (>= EDT_NOSITE everywhere when there is none).  scratch: an int32 volume of the same shape to reuse between calls"""
+        self._chk(sites, scratch)
+        if sites.dtype != torch.uint8 or sites.dim() != 3:
+            raise _lib.BcpError("edt_sq: a uint8 [D,H,W] volume")
+        D, H, W = sites.shape
+        out = torch.empty(sites.shape, dtype=torch.int32, device=sites.device)
+        if scratch is None:
+            scratch = torch.empty_like(out)
+        elif scratch.dtype != torch.int32 or scratch.shape != out.shape or scratch.device != out.device:
+            raise _lib.BcpError("edt_sq: scratch must be an int32 volume of the sites' shape on their device")
+        self.b.call("bcp_edt_sq", _p(sites), D, H, W, _p(out), _p(scratch), self.stream(sites))
+        return out
+
+    @staticmethod
+    def surface_bins(shape):
+        """bins bcp_surface_hist needs for a [D,H,W] volume: the largest squared distance inside it, plus one"""
+        return sum((int(s) - 1) ** 2 for s in shape) + 1
+
+    def surface_hist(self, border_from, d2_to, nbins=None):
+        """-> int64 [nbins] device tensor: histogram of d2_to (int32 squared distances) over the voxels where border_from (uint8) is nonzero
+        (the library's bins are uint32; widened here so that no caller has to remember the sign bit)"""
+        self._chk(border_from, d2_to)
+        if border_from.dtype != torch.uint8 or d2_to.dtype != torch.int32 or border_from.dim() != 3 or d2_to.shape != border_from.shape:
+            raise _lib.BcpError("surface_hist: a uint8 [D,H,W] border map and an int32 volume of the same shape")
+        D, H, W = border_from.shape
+        if nbins is None:
+            nbins = self.surface_bins(border_from.shape)
+        hist = torch.empty(int(nbins), dtype=torch.int32, device=border_from.device)
+        self.b.call("bcp_surface_hist", _p(border_from), _p(d2_to), D, H, W, _p(hist), int(nbins), self.stream(border_from))
+        return hist.to(torch.int64) & 0xFFFFFFFF
 
     def crop_rotflip(self, src, patch, k, flip_axis, pads, origin):
         """src [n0,n1,n2] float32 or uint8 -> [P0,P1,P2]: RandomRotFlip + RandomCrop (dataloaders/dataset.py) as one gather"""

@@ -99,10 +99,8 @@ def _val_set(device, n, seed=seed_test + 77):
     return [(vols[i, 0].to(device), labs[i].to(device)) for i in range(max(n, 1))]
 
 
-def main(argv=None):
-    from pathlib import Path
-    from bcp_amd.pancreas.pancreas_utils import load_net_opt, save_net, save_net_opt
-    from bcp_amd.pancreas.test_util import test_calculate_metric
+def build_parser():
+    """the command line of main()"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--pretraining_epochs", type=int, default=pretraining_epochs)
     ap.add_argument("--self_training_epochs", type=int, default=self_training_epochs)
@@ -116,9 +114,19 @@ def main(argv=None):
     ap.add_argument("--list_dir", type=str, default="", help="directory holding <split_name>/<10|20>percent/{train_lab,train_unlab,test}.txt (the reference hard-codes its own, pancreas/dataloaders.py:103-106)")
     ap.add_argument("--labelp", type=int, default=10)
     ap.add_argument("--device_input_pipeline", type=int, default=0, help="1: draw every batch from the four loader streams of the reference (RandomCrop / CenterCrop to 96^3, pancreas/dataloaders.py) with the crops done on the device")
+    ap.add_argument("--val_surface", action="store_true",
+                    help="validation also computes medpy's hd95 / asd on the device (utils/surface.py) and logs their means; checkpoints are still chosen by Dice, as in the reference")
     ap.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
                     help="the copy-paste region: box = one 64^3 box (the reference's loop), random = 27 small boxes, concat = one slab along z (utils/BCP_utils.py:30-56)")
-    args = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    from pathlib import Path
+    from bcp_amd.pancreas.pancreas_utils import load_net_opt, save_net, save_net_opt
+    from bcp_amd.pancreas.test_util import test_calculate_metric
+    from bcp_amd.utils.surface import pancreas_calculate_metric
+    args = build_parser().parse_args(argv)
     strategy = train_step.cli_mask_strategy(args.mask_strategy)
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
     np.random.seed(seed_test)
@@ -140,7 +148,11 @@ def main(argv=None):
         st_dir.mkdir(parents=True, exist_ok=True)
 
     def validate(model):
-        avg, _ = test_calculate_metric(model, val, num_classes=2, dim=(96, 96, 96), s_xy=args.val_stride[0], s_z=args.val_stride[1])
+        if args.val_surface:      # the same loop with medpy's hd95 / asd where test_calculate_metric reports nan (utils/surface.py)
+            avg, _ = pancreas_calculate_metric(model, val, num_classes=2, dim=(96, 96, 96), s_xy=args.val_stride[0], s_z=args.val_stride[1])
+            logging.info("Evaluation: val_hd95: %.4f, val_asd: %.4f", float(avg[2]), float(avg[3]))
+        else:
+            avg, _ = test_calculate_metric(model, val, num_classes=2, dim=(96, 96, 96), s_xy=args.val_stride[0], s_z=args.val_stride[1])
         return float(avg[0])
 
     max_dice, best_pre = -1.0, pre_dir / f"best_ema{label_percent}_pre.pth"

@@ -1,12 +1,12 @@
 """Counterpart of code/utils/val_2d.py (ACDC): per-volume validation of the 2-D U-Net in eval() mode.
 
-  test_single_volume(image [1,S,X,Y], label [1,S,X,Y], model, classes, patch_size=[256,256]) -> [(dice, hd95)] * (classes-1)
+  test_single_volume(image [1,S,X,Y], label [1,S,X,Y], model, classes, patch_size=[256,256], surface=False) -> [(dice, hd95)] * (classes-1)
 
 Nothing leaves the device: slices of another size than patch_size are zoomed to it and the label maps back with the same
 nearest-neighbour gather that restates scipy.ndimage.zoom(order=0) (val_2d.py:26,35; csrc/eval.hip k_acdc_augment), all slices
 of the volume go through the net in batches (eval-mode BatchNorm is per element, so batching changes nothing), softmax + argmax
 is the pseudo-label kernel (first maximum wins, as torch.argmax), per-class overlap counts are integer atomics.
-hd95 is medpy CPU code: reported as nan.
+hd95 is nan by default; surface=True computes medpy's hd95 of the [S,X,Y] volume per class on the device (utils/surface.py).
 """
 from __future__ import annotations
 
@@ -21,16 +21,20 @@ def _ops_for(t):
     return Ops.product() if t.is_cuda else BU._cpu_ops()
 
 
-def calculate_metric_percase(pred_u8, gt_u8, cls):
-    """:9-17 on the device: (dice, hd95) of (pred == cls, gt == cls); (0, 0) when the prediction is empty"""
+def calculate_metric_percase(pred_u8, gt_u8, cls, surface=False):
+    """:9-17 on the device: (dice, hd95) of (pred == cls, gt == cls); (0, 0) when the prediction is empty.  hd95 is nan unless
+    surface=True (an empty label under a non-empty prediction then raises RuntimeError, as medpy does in the reference)"""
     inter, a, b = _ops_for(pred_u8).overlap_counts(pred_u8, gt_u8, cls).tolist()
     if a == 0:
         return 0, 0
     dice = 2.0 * inter / (a + b) if (a + b) > 0 else 0.0
-    return dice, float("nan")
+    if not surface:
+        return dice, float("nan")
+    from . import surface as S
+    return dice, S.hd95_asd(pred_u8, gt_u8, cls)[0]
 
 
-def test_single_volume(image, label, model, classes, patch_size=(256, 256), batch=16):
+def test_single_volume(image, label, model, classes, patch_size=(256, 256), batch=16, surface=False):
     device = next(model.parameters()).device
     image = image.squeeze(0).to(device=device, dtype=torch.float32)
     label = label.squeeze(0).to(device)
@@ -61,7 +65,7 @@ def test_single_volume(image, label, model, classes, patch_size=(256, 256), batc
         model.train(was_training)
     gt = label.to(torch.uint8).contiguous()
     prediction = prediction.contiguous()
-    return [calculate_metric_percase(prediction, gt, i) for i in range(1, classes)]
+    return [calculate_metric_percase(prediction, gt, i, surface=surface) for i in range(1, classes)]
 
 
 test_single_volume.__test__ = False   # name mirrors the reference module; not a pytest test

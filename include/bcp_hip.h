@@ -42,7 +42,7 @@ enum { BCP_WG_DOWN = 0, BCP_WG_UP = 1, BCP_WG_PW = 2 };
 /* ABI revision = 100 * round + change counter.  Bumped whenever an exported signature changes; a binding must refuse a library whose
  * bcp_version() differs from the header it was written against (bcp_amd/_lib.py does: a stale in-tree .so then fails at load, not
  * with shifted arguments inside a launch). */
-#define BCP_ABI_VERSION 512
+#define BCP_ABI_VERSION 513
 int bcp_version(void);
 const char* bcp_last_error(void);
 /* process-wide tuning / test switches (the library never reads the environment): name = a field of bcp::Options
@@ -403,6 +403,27 @@ int bcp_sw_accumulate(const float* logits_patch, float* score, float* cnt, int X
 int bcp_sw_finish(float* score, const float* cnt, uint8_t* label, long long n, float thres, void* stream);
 int bcp_overlap_counts(const uint8_t* pred, const uint8_t* gt, long long n, int cls /* 0: != 0; > 0: == cls */, unsigned long long* counts,
                        void* stream);
+
+/* ---- surface distances on the device: medpy.metric.binary.hd95 / asd as the reference calls them (utils/test_3d_patch.py:269-273,
+ *      pancreas/test_util.py:20-24, utils/val_2d.py:9-17, test_ACDC.py:26-33: unit voxel spacing, connectivity 1), in integers.
+ *      Volumes are contiguous [D][H][W], every extent in 1..1024.  Each call refuses (BCP_EINVAL, bcp_last_error) null pointers, an
+ *      extent outside 1..1024, cls outside 0..255 and too few bins before it launches anything.
+ *      bcp_surface_border: border[v] = sel(seg[v]) and some 6-neighbour is outside the volume or not selected -- medpy's
+ *        m ^ binary_erosion(m, generate_binary_structure(3, 1)) with border_value 0; sel as in bcp_overlap_counts (cls 0: != 0,
+ *        cls > 0: == cls).  count: device uint64 (zeroed by the call) = number of border voxels.
+ *      bcp_edt_sq: out[v] = exact squared Euclidean distance (voxels) from v to the nearest nonzero voxel of `sites` -- the square of
+ *        scipy.ndimage.distance_transform_edt(~sites), which medpy samples at the other object's border.  Separable: one pass along W,
+ *        then min_j (g[j] + (i - j)^2) along H and along D.  scratch: caller-owned int32 volume of the same size, not `out`.  A line
+ *        without a site carries BCP_EDT_NOSITE (at most 3 * 1023^2 < 2^22 is ever added: no overflow); when `sites` is all zero every
+ *        out[v] >= BCP_EDT_NOSITE.
+ *      bcp_surface_hist: hist[d2_to[v]] += 1 for every v with border_from[v] != 0.  hist: device uint32[nbins], zeroed by the call;
+ *        nbins >= (D-1)^2 + (H-1)^2 + (W-1)^2 + 1.  A value outside the bins (an all-zero site map) is not counted.
+ *      Integer atomics only: every output is deterministic. */
+#define BCP_EDT_NOSITE (1 << 30)
+int bcp_surface_border(const uint8_t* seg, int D, int H, int W, int cls /* 0: != 0; > 0: == cls */, uint8_t* border,
+                       unsigned long long* count, void* stream);
+int bcp_edt_sq(const uint8_t* sites, int D, int H, int W, int32_t* out, int32_t* scratch, void* stream);
+int bcp_surface_hist(const uint8_t* border_from, const int32_t* d2_to, int D, int H, int W, unsigned* hist, int nbins, void* stream);
 
 /* ---- device-side input pipeline, LA: RandomRotFlip + RandomCrop of dataloaders/dataset.py:52-59,173-214 as one
  *      gather: dst[P0][P1][P2] = pad(flip(rot90(src[n0][n1][n2], k, axes=(0,1)), flip_axis), (pw,ph,pd))[w1:, h1:, d1:];
