@@ -3,6 +3,7 @@ Module-level constants mirror :22-48.  Four streams (lab_a, lab_b, unlab_a, unla
 each, Adam(1e-3), u_weight left at mix_loss's default 0.5 exactly as the reference calls it (:160,164).
 
   python -m bcp_amd.pancreas.train_pancreas --pretraining_epochs 1 --self_training_epochs 1 --steps_per_epoch 3
+  python -m bcp_amd.pancreas.train_pancreas --test        (the reference's closing test_model call, :181-195; off by default)
 """
 import argparse
 import logging
@@ -99,6 +100,31 @@ def _val_set(device, n, seed=seed_test + 77):
     return [(vols[i, 0].to(device), labs[i].to(device)) for i in range(max(n, 1))]
 
 
+def test_model(net, test_set, load_path=None, dim=(96, 96, 96)):
+    """train_pancreas.py:181-187: the test pass with all four metrics -> (avg_metric [dice, jc, hd95, asd], metric_list).  load_path: a
+    checkpoint to read first (the reference always reads one; here the net in hand is evaluated when none is given).  test_set: an
+    iterable of (image [W,H,D], label [W,H,D]).  dim: the sliding-window patch (test_calculate_metric's default)."""
+    from bcp_amd.utils.evaluate import load_weights
+    from bcp_amd.utils.surface import pancreas_calculate_metric
+    if load_path is not None:
+        load_weights(net, load_path)
+        print('Successful Loaded')
+    return pancreas_calculate_metric(net, test_set, dim=tuple(dim), s_xy=16, s_z=4)
+
+
+test_model.__test__ = False   # name mirrors the reference; not a pytest test
+
+
+def _test_set(args, device):
+    """the cases of the test pass: the whole volumes of Pancreas(split="test") (the reference walks `test_dataset.image_list`, not the
+    cropped items: pancreas/test_util.py:190-195), or the synthetic set"""
+    if args.data_root and args.list_dir:
+        from bcp_amd.pancreas.dataloaders import Pancreas
+        ds = Pancreas(args.data_root, "pancreas", split="test", labelp=args.labelp, list_dir=args.list_dir, device=device)
+        return [ds._cache.get(path) for path in ds.image_list]
+    return _val_set(device, args.val_cases, seed=seed_test + 78)
+
+
 def build_parser():
     """the command line of main()"""
     ap = argparse.ArgumentParser()
@@ -116,6 +142,9 @@ def build_parser():
     ap.add_argument("--device_input_pipeline", type=int, default=0, help="1: draw every batch from the four loader streams of the reference (RandomCrop / CenterCrop to 96^3, pancreas/dataloaders.py) with the crops done on the device")
     ap.add_argument("--val_surface", action="store_true",
                     help="validation also computes medpy's hd95 / asd on the device (utils/surface.py) and logs their means; checkpoints are still chosen by Dice, as in the reference")
+    ap.add_argument("--test", action="store_true",
+                    help="after self-training, run the reference's test pass (test_model, train_pancreas.py:181-195: sliding window at strides 16 / 4, "
+                         "Dice, Jaccard, 95HD, ASD) over the test split and log the four averages")
     ap.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
                     help="the copy-paste region: box = one 64^3 box (the reference's loop), random = 27 small boxes, concat = one slab along z (utils/BCP_utils.py:30-56)")
     return ap
@@ -180,6 +209,11 @@ def main(argv=None):
             logging.info("Evaluation: val_dice: %.4f, val_maxdice: %.4f", val_dice, max_dice)
         loss = ema_cutmix(net, ema_net, optimizer, streams, args.steps_per_epoch, mask_strategy=strategy)
         logging.info("self-train epoch %d loss %f", ep, float(loss.detach()))
+    if args.test:                                                     # :195 -- the best self-trained checkpoint when validation wrote one, else the net in hand
+        best_self = st_dir / f"best_ema_{label_percent}_self.pth"
+        avg_metric, _ = test_model(net, _test_set(args, device), load_path=best_self if val is not None and best_self.exists() else None)
+        logging.info("Test: dice: %.4f, jc: %.4f, hd95: %.4f, asd: %.4f", *(float(v) for v in avg_metric))
+        return avg_metric
 
 
 if __name__ == "__main__":

@@ -25,6 +25,7 @@ slots and launch nothing new; these are their counterparts with the slots filled
 
   calculate_metric_percase(pred, gt) -> (dice, jc, hd95, asd)                                   (utils/test_3d_patch.py:180-186, :269-273)
   la_all_case(model, cases, num_classes, patch_size, stride_xy, stride_z, nms=0) -> avg[4]       (utils/test_3d_patch.py:40-80)
+  acdc_case_metrics(pred, gt, surface=True, classes=4) -> [(dice, jc, hd95, asd)] * (classes-1)  (test_ACDC.py:55-68, per class over [S,X,Y])
   pancreas_all_case(net, cases, num_classes, patch_size, stride_xy, stride_z, nms=0) -> (avg[4], metric_list)   (pancreas/test_util.py:152-185)
   pancreas_calculate_metric(net, test_dataset, num_classes=2, dim=(96, 96, 96), s_xy=18, s_z=4, pancreas=True, DTC=False, nms=0) -> the same  (:188-199)
 
@@ -108,22 +109,50 @@ def calculate_metric_percase(pred, gt):
     return dc, jc, hd, asd
 
 
-def _all_case(predict, cases, nms):
+def _all_case(predict, cases, nms, surface=True, on_case=None):
+    """surface=False: the two surface slots are nan and none of the surface kernels runs (what test_3d_patch.calculate_metric_percase
+    reports).  on_case(ith, image, label, prediction, single_metric) is called once per case, after its metrics (the offline evaluation's
+    per-case line and --save_result)."""
+    from . import test_3d_patch as T3
+    percase = calculate_metric_percase if surface else T3.calculate_metric_percase
     total, metric_list = np.zeros(4), []
-    for image, label in cases:
+    for ith, (image, label) in enumerate(cases):
         prediction = predict(image)
         if nms:
             prediction = _ops_for(prediction).cc_largest(prediction.to(torch.uint8).unsqueeze(0).contiguous(), 1, 3)[0]
-        single = (0, 0, 0, 0) if int(prediction.sum()) == 0 else calculate_metric_percase(prediction, label)
+        single = (0, 0, 0, 0) if int(prediction.sum()) == 0 else percase(prediction, label)
         total += np.asarray(single, dtype=np.float64)
         metric_list.append(single)
+        if on_case is not None:
+            on_case(ith, image, label, prediction, single)
     return total / max(len(metric_list), 1), metric_list
 
 
-def la_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, nms=0):
+def la_all_case(model, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, nms=0, surface=True, on_case=None):
     """test_3d_patch.test_all_case with the surface distances: per-case (dice, jc, hd95, asd), averaged"""
     from . import test_3d_patch as T3
-    return _all_case(lambda image: T3.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes)[0], cases, nms)[0]
+    return _all_case(lambda image: T3.test_single_case(model, image, stride_xy, stride_z, patch_size, num_classes=num_classes)[0], cases, nms,
+                     surface, on_case)[0]
+
+
+def acdc_case_metrics(pred_u8, gt_u8, surface=True, classes=4):
+    """test_ACDC.py:55-68 for two label volumes [S,X,Y] (uint8 device tensors or arrays): [(dice, jc, hd95, asd)] * (classes - 1) of
+    (pred == c, gt == c) for c = 1..classes-1.  (0, 0, 0, 0) when the prediction has no voxel of class c; RuntimeError, as medpy raises,
+    when the label has none but the prediction does.  surface=False: hd95 / asd are nan, no surface kernel runs and nothing raises."""
+    device = pred_u8.device if isinstance(pred_u8, torch.Tensor) else (gt_u8.device if isinstance(gt_u8, torch.Tensor) else torch.device("cpu"))
+    p, g = _as_u8(pred_u8, device, 1), _as_u8(gt_u8, device, 1)
+    ops = _ops_for(p)
+    out = []
+    for cls in range(1, classes):
+        inter, a, b = ops.overlap_counts(p, g, cls).tolist()
+        if a == 0:
+            out.append((0, 0, 0, 0))
+            continue
+        dc = 2.0 * inter / (a + b)
+        jc = inter / (a + b - inter)
+        hd, asd = hd95_asd(p, g, cls) if surface else (float("nan"), float("nan"))
+        out.append((dc, jc, hd, asd))
+    return out
 
 
 def pancreas_all_case(net, cases, num_classes, patch_size=(112, 112, 80), stride_xy=18, stride_z=4, nms=0, TMI=0):

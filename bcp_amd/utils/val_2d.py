@@ -1,6 +1,7 @@
 """Counterpart of code/utils/val_2d.py (ACDC): per-volume validation of the 2-D U-Net in eval() mode.
 
   test_single_volume(image [1,S,X,Y], label [1,S,X,Y], model, classes, patch_size=[256,256], surface=False) -> [(dice, hd95)] * (classes-1)
+  predict_volume(image [S,X,Y], model, patch_size=[256,256], batch=16) -> uint8 label volume [S,X,Y]     (the part test_ACDC.py shares)
 
 Nothing leaves the device: slices of another size than patch_size are zoomed to it and the label maps back with the same
 nearest-neighbour gather that restates scipy.ndimage.zoom(order=0) (val_2d.py:26,35; csrc/eval.hip k_acdc_augment), all slices
@@ -34,10 +35,10 @@ def calculate_metric_percase(pred_u8, gt_u8, cls, surface=False):
     return dice, S.hd95_asd(pred_u8, gt_u8, cls)[0]
 
 
-def test_single_volume(image, label, model, classes, patch_size=(256, 256), batch=16, surface=False):
-    device = next(model.parameters()).device
-    image = image.squeeze(0).to(device=device, dtype=torch.float32)
-    label = label.squeeze(0).to(device)
+def predict_volume(image, model, patch_size=(256, 256), batch=16):
+    """the label volume of one case (val_2d.py:23-36, test_ACDC.py:40-54): image [S,X,Y] float32 on the model's device -> uint8 [S,X,Y].
+    Slices of another size than patch_size are zoomed to it, the eval-mode net runs `batch` slices per call, the first maximum wins,
+    the label map is zoomed back.  Shared by test_single_volume below and the offline evaluation (bcp_amd/test_ACDC.py)."""
     S, x, y = image.shape
     ops = _ops_for(image)
     was_training = model.training
@@ -63,8 +64,15 @@ def test_single_volume(image, label, model, classes, patch_size=(256, 256), batc
             prediction = torch.cat(preds)
     finally:
         model.train(was_training)
+    return prediction.contiguous()
+
+
+def test_single_volume(image, label, model, classes, patch_size=(256, 256), batch=16, surface=False):
+    device = next(model.parameters()).device
+    image = image.squeeze(0).to(device=device, dtype=torch.float32)
+    label = label.squeeze(0).to(device)
+    prediction = predict_volume(image, model, patch_size, batch)
     gt = label.to(torch.uint8).contiguous()
-    prediction = prediction.contiguous()
     return [calculate_metric_percase(prediction, gt, i, surface=surface) for i in range(1, classes)]
 
 
