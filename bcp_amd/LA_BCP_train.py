@@ -43,6 +43,9 @@ for _name, _type, _default, _help in _BUILD_FLAGS:
 parser.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
                     help="the copy-paste region: box = one 2/3-side box (context_mask, the reference's command line), random = 27 small boxes "
                          "(utils/BCP_utils.py:30 random_mask), concat = one slab along z (:48 concate_mask)")
+parser.add_argument("--normalization", type=str, default="batchnorm", choices=("batchnorm", "groupnorm"),
+                    help="the V-Net's norm layers: batchnorm (the reference's command line) or groupnorm = nn.GroupNorm(16, C) (networks/VNet.py:20-21): "
+                         "per-sample statistics, so the result does not depend on how the batch is cut across ranks")
 parser.add_argument("--augment", action="store_true",
                     help="cases larger than the patch + the device-side RandomRotFlip / RandomCrop (dataloaders/dataset.py)")
 
@@ -140,7 +143,7 @@ class _BestModel:
 
 
 def pre_train(args, snapshot_path, device):
-    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train")
+    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
     db_train, sampler = _data(args, device)
     optimizer = _optimizer(args, model)
     model.train()
@@ -160,8 +163,8 @@ def pre_train(args, snapshot_path, device):
 
 
 def self_train(args, pre_snapshot_path, self_snapshot_path, device):
-    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train")
-    ema_model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train")
+    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
+    ema_model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
     for p in ema_model.parameters():
         p.detach_()                     # the teacher never sees a gradient
     model.volatile_io = ema_model.volatile_io = True      # this loop consumes a pass's outputs before the network's next pass (networks/_hipnet.py)

@@ -13,6 +13,7 @@
 //   groups G = 1            : BatchNorm over all rows (N*spatial)
 //   groups G = N            : InstanceNorm, rows_per_group = spatial
 #include "common.h"
+#include "norm_shared.h"
 #include "../../include/bcp_hip.h"
 
 namespace bcp {
@@ -206,39 +207,7 @@ __global__ __launch_bounds__(256) void k_col_partial(const float* __restrict__ y
   }
 }
 
-// Sum the per-block partials of 16 channels of one group: 1024 threads = 32 doubles (16 channels x {s1, s2}, one 256-byte
-// row of the partial table) x 32 row-slots, four independent loads in flight per thread, then an LDS tree.  Threads 0..15
-// return true with the two sums of channel chunk*16 + tid.  (A single thread walking ~1000 partials serially cost more than
-// the streaming pass itself; 16 slots with one load in flight left this kernel at ~8 us on the step's critical path.)
-constexpr int kFinalizeThreads = 1024;
-__device__ __forceinline__ bool reduce_partials(const double* __restrict__ partial, int nb, int C, int g, int chunk,
-                                                double& s1, double& s2) {
-  __shared__ double red[32][33];
-  __shared__ double fin[32];
-  const int e = threadIdx.x & 31, slot = threadIdx.x >> 5;
-  const double* p = partial + ((long long)g * nb * C + chunk * 16) * 2 + e;
-  const long long rs = (long long)C * 2;
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  int b = slot;
-  for (; b + 96 < nb; b += 128) {
-    const double v0 = p[b * rs], v1 = p[(b + 32) * rs], v2 = p[(b + 64) * rs], v3 = p[(b + 96) * rs];
-    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
-  }
-  for (; b < nb; b += 32) a0 += p[b * rs];
-  red[slot][e] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (threadIdx.x < 32) {
-    double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-    for (int k = 0; k < 32; k += 2) { t0 += red[k][e]; t1 += red[k + 1][e]; }
-    fin[e] = t0 + t1;
-  }
-  __syncthreads();
-  if (threadIdx.x >= 16) return false;
-  s1 = fin[threadIdx.x * 2];
-  s2 = fin[threadIdx.x * 2 + 1];
-  return true;
-}
+// reduce_partials (the sum of the per-block partial rows, 16 channels of one group per workgroup): csrc/norm_shared.h
 
 // forward finalize: block = (group g, 16-channel chunk)
 __global__ __launch_bounds__(kFinalizeThreads) void k_norm_finalize(const double* __restrict__ partial, int nb, int G, int C,
@@ -1157,6 +1126,33 @@ void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long 
   if (!skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, dgamma, dbeta,
                      accumulate, c1, c2, raw, amax_clear_or_null);
   if (dgamma) hipLaunchKernelGGL(k_norm_bwd_params, dim3(1), dim3(256), 0, s, raw, G, C, dgamma, dbeta, accumulate);
+}
+
+// ---- the per-sample streams a GroupNorm layer shares with the layers above (csrc/gnorm.hip; declarations: csrc/norm_shared.h): the same
+// kernels, launched with one group per sample.  GroupNorm forms its table and its backward coefficients in finalize kernels of its own.
+int per_sample_stat_rows(long long rows_per_sample, int C) { return norm_blocks(rows_per_sample, C); }
+int per_sample_apply_blocks(long long rows_per_sample, int C, int N) { return apply_grid(rows_per_sample * (C / 4), N); }
+
+void per_sample_stats_launch(const float* y, int N, long long rows_per_sample, int C, double* partial, hipStream_t s) {
+  const NormEpilogue ep{nullptr, nullptr, 1.f, rows_per_sample, ACT_NONE, nullptr, 0.f};
+  hipLaunchKernelGGL((k_col_partial<0>), dim3(norm_blocks(rows_per_sample, C), N), dim3(256), 0, s, y, (const float*)nullptr, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ep, rows_per_sample, 1, C, partial, SlabSrc{}, (float*)nullptr);
+}
+
+void per_sample_bwd_stats_launch(const float* y, const float* da, const float* table, int N, long long rows_per_sample, int C, int act,
+                                 const float* chan_scale, double* partial, hipStream_t s) {
+  const NormEpilogue ep{chan_scale, nullptr, 1.f, rows_per_sample, act, nullptr, 0.f};
+  const float *mean = table, *rstd = table + (long long)N * C, *scale = table + 2LL * N * C, *shift = table + 3LL * N * C;
+  hipLaunchKernelGGL((k_col_partial<1>), dim3(norm_blocks(rows_per_sample, C), N), dim3(256), 0, s, y, da, scale, shift, mean, rstd, ep, rows_per_sample, 1,
+                     C, partial, SlabSrc{}, (float*)nullptr);
+}
+
+void per_sample_apply_launch(const float* y, const float* table, int N, long long rows_per_sample, int C, int act, const float* chan_scale,
+                             const float* residual, float* out, float* amax_out, hipStream_t s) {
+  const NormEpilogue ep{chan_scale, nullptr, 1.f, rows_per_sample, act, nullptr, 0.f};
+  const float *mean = table, *scale = table + 2LL * N * C, *shift = table + 3LL * N * C, *row4 = table + 4LL * N * C;
+  hipLaunchKernelGGL(k_norm_apply, dim3(apply_grid(rows_per_sample * (C / 4), N), N), dim3(256), 0, s, y, scale, shift, mean, residual, ep, rows_per_sample, 1,
+                     N, C, out, row4, (float*)nullptr, (float*)nullptr, 0.f, amax_out, (long long)(C / 4));
 }
 
 }  // namespace bcp

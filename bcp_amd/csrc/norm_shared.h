@@ -1,0 +1,56 @@
+// bcp_amd/csrc/norm_shared.h -- what csrc/norm.hip (BatchNorm / InstanceNorm) shares with csrc/gnorm.hip (GroupNorm): the reduction of the
+// per-block fp64 partial rows, and host launchers for the per-sample statistics / apply streams that GroupNorm runs unchanged (G = N).
+#pragma once
+#include "common.h"
+
+namespace bcp {
+
+// Sum the per-block partials of 16 channels of one group: 1024 threads = 32 doubles (16 channels x {s1, s2}, one 256-byte
+// row of the partial table) x 32 row-slots, four independent loads in flight per thread, then an LDS tree.  Threads 0..15
+// return true with the two sums of channel chunk*16 + tid.  (A single thread walking ~1000 partials serially cost more than
+// the streaming pass itself; 16 slots with one load in flight left this kernel at ~8 us on the step's critical path.)
+constexpr int kFinalizeThreads = 1024;
+__device__ __forceinline__ bool reduce_partials(const double* __restrict__ partial, int nb, int C, int g, int chunk,
+                                                double& s1, double& s2) {
+  __shared__ double red[32][33];
+  __shared__ double fin[32];
+  const int e = threadIdx.x & 31, slot = threadIdx.x >> 5;
+  const double* p = partial + ((long long)g * nb * C + chunk * 16) * 2 + e;
+  const long long rs = (long long)C * 2;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  int b = slot;
+  for (; b + 96 < nb; b += 128) {
+    const double v0 = p[b * rs], v1 = p[(b + 32) * rs], v2 = p[(b + 64) * rs], v3 = p[(b + 96) * rs];
+    a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+  }
+  for (; b < nb; b += 32) a0 += p[b * rs];
+  red[slot][e] = (a0 + a1) + (a2 + a3);
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+    for (int k = 0; k < 32; k += 2) { t0 += red[k][e]; t1 += red[k + 1][e]; }
+    fin[e] = t0 + t1;
+  }
+  __syncthreads();
+  if (threadIdx.x >= 16) return false;
+  s1 = fin[threadIdx.x * 2];
+  s2 = fin[threadIdx.x * 2 + 1];
+  return true;
+}
+
+// ---- per-sample streams of csrc/norm.hip launched for a GroupNorm layer (groups of the streams = samples; table = float[5][N][C])
+// partial rows per sample the statistics passes below leave (the workspace holds N x this many rows of [C][2] doubles)
+int per_sample_stat_rows(long long rows_per_sample, int C);
+// k_col_partial<0>: (sum y, sum y^2) per (sample, block, channel)
+void per_sample_stats_launch(const float* y, int N, long long rows_per_sample, int C, double* partial, hipStream_t s);
+// k_col_partial<1>: (sum dz, sum dz * xhat) per (sample, block, channel), xhat and the activation pattern from the table
+void per_sample_bwd_stats_launch(const float* y, const float* da, const float* table, int N, long long rows_per_sample, int C, int act,
+                                 const float* chan_scale, double* partial, hipStream_t s);
+// k_norm_apply: a = act((y - mean) * scale + shift) [* chan_scale] [+ residual], |max| of a into amax_out's slots
+void per_sample_apply_launch(const float* y, const float* table, int N, long long rows_per_sample, int C, int act, const float* chan_scale,
+                             const float* residual, float* out, float* amax_out, hipStream_t s);
+// the grid the apply passes are sized for (norm_apply_cap / norm_apply_vec options included)
+int per_sample_apply_blocks(long long rows_per_sample, int C, int N);
+
+}  // namespace bcp

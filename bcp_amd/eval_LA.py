@@ -1,0 +1,37 @@
+"""test_LA for checkpoints of a V-Net with another normalisation: the command line and the flow of bcp_amd/test_LA.py (the reference's
+code/test_LA.py:9-52 plus this build's flags), plus `--normalization {batchnorm,groupnorm}` -- the norm layers the checkpoint was trained
+with (`LA_BCP_train --normalization`, networks/VNet.py:20-21).
+
+Why a module of its own: bcp_amd/test_LA.py carries a `test_*.py` name, and a feature change leaves every existing `test_*.py` file
+byte-identical, so the option cannot be added there.  This module takes test_LA's parser as its parent and runs
+test_LA's own `test_calculate_metric` with the factory bound to the chosen normalisation; nothing else differs.  A checkpoint of the other
+normalisation fails in `load_state_dict`.
+
+  python -m bcp_amd.eval_LA --labelnum 8 --stage_name self_train --normalization groupnorm
+"""
+import argparse
+import functools
+import logging
+import sys
+
+from bcp_amd import test_LA as _T
+from bcp_amd.networks.net_factory import net_factory
+
+parser = argparse.ArgumentParser(parents=[_T.parser], conflict_handler="resolve")
+parser.add_argument("--normalization", type=str, default="batchnorm", choices=("batchnorm", "groupnorm"),
+                    help="the norm layers the checkpoint was trained with (LA_BCP_train --normalization); a checkpoint of the other kind fails to load")
+
+
+def main(argv=None):
+    FLAGS = parser.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="[%(asctime)s.%(msecs)03d] %(message)s", datefmt="%H:%M:%S", stream=sys.stdout)
+    factory = _T.net_factory
+    _T.net_factory = functools.partial(net_factory, normalization=FLAGS.normalization)
+    try:
+        return _T.test_calculate_metric(FLAGS)
+    finally:
+        _T.net_factory = factory
+
+
+if __name__ == "__main__":
+    print(main())

@@ -533,6 +533,41 @@ class Ops:
                     em_seed, em_keep, _p(dgamma), _p(dbeta), int(bool(accumulate)), _p(ws), _p(partial), int(nb), _p(out), _p(self._amax_slot(out, backward=True)), self.stream(y))
         return out
 
+    # ------------------------------------------------------------------ GroupNorm (nn.GroupNorm(16, C): normalization='groupnorm' of the V-Nets)
+    GN_GROUPS = 16
+
+    def gnorm_fwd(self, y, gamma, beta, act, out=None, chan_scale=None, residual=None, eps=1e-5, partial=None, nb=0, stats_only=False):
+        """y [N,D,H,W,C] -> (a, stats[5,N,C]): GroupNorm over 16 groups of C/16 adjacent channels per sample, + activation, Dropout3d
+        channel scale and residual.  partial / nb: the per-sample statistics rows a *_fwd_stats epilogue left (groups = N).  stats_only:
+        the table without the apply pass (the consumer normalises on its way in); returns (None, stats)."""
+        self._chk(y, gamma, beta, chan_scale, residual, out)
+        N, Cc = y.shape[0], y.shape[-1]
+        rps = y.numel() // (Cc * N)
+        ws = self.workspace("gnorm", self._ws_bytes("bcp_gnorm_workspace_bytes", N, rps, Cc), y)
+        stats = torch.empty((5, N, Cc), dtype=torch.float32, device=y.device)
+        if stats_only:
+            assert out is None and residual is None
+        elif out is None:
+            out = torch.empty_like(y)
+        amax = self._amax_slot(out)
+        self.b.call("bcp_gnorm_fwd", _p(y), N, rps, Cc, self.GN_GROUPS, _p(gamma), _p(beta), float(eps), act, _p(chan_scale), _p(residual),
+                    _p(stats), _p(ws), _p(partial), int(nb), _p(out), _p(amax), self.stream(y))
+        return out, stats
+
+    def gnorm_bwd(self, y, da, stats, gamma, act, dgamma=None, dbeta=None, dbias=None, accumulate=False, chan_scale=None, out=None,
+                  partial=None, nb=0):
+        """-> dy; dgamma / dbeta (a pair) and dbias -- the gradient of the bias of the conv that produced y, exact zeros for C = 16 --
+        are written or, with accumulate, added to.  partial / nb: per-sample backward-statistics rows a *_dgrad_bwdstats epilogue left."""
+        self._chk(y, da, stats, gamma, dgamma, dbeta, dbias, chan_scale, out)
+        N, Cc = y.shape[0], y.shape[-1]
+        rps = y.numel() // (Cc * N)
+        ws = self.workspace("gnorm", self._ws_bytes("bcp_gnorm_workspace_bytes", N, rps, Cc), y)
+        if out is None:
+            out = torch.empty_like(y)
+        self.b.call("bcp_gnorm_bwd", _p(y), _p(da), N, rps, Cc, self.GN_GROUPS, _p(stats), _p(gamma), act, _p(chan_scale), _p(dgamma), _p(dbeta),
+                    _p(dbias), int(bool(accumulate)), _p(ws), _p(partial), int(nb), _p(out), _p(self._amax_slot(out, backward=True)),
+                    self.stream(y))
+        return out
 
     # ------------------------------------------------------------------ deep levels: the norm takes the conv's raw split-K slabs
     def norm_slabs_ok(self, G, rows_per_group, Cc):
@@ -1119,7 +1154,7 @@ class Ops:
 # ---------------------------------------------------------------------------------------------- measurement hooks
 # bench.py's per-op table: HIP events on the launch stream around every call of the ops below while a profile is open
 # (Ops.profile_begin / profile_end).  Closed (the default) the wrappers cost one attribute test.
-_PROFILED = ("mix_box", "plabel_bin", "plabel_argmax4", "cc_largest", "plabel_cc_largest", "mixloss_fwd", "mixloss_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd", "norm_fwd", "norm_bwd", "norm_fwd_slabs", "norm_bwd_slabs", "conv3_fwd_raw", "conv3_dgrad_bwdstats", "pw16_bwd_norm_bwd", "conv3_c1_norm_bwd_wgrad", "conv3_pack_many",
+_PROFILED = ("mix_box", "plabel_bin", "plabel_argmax4", "cc_largest", "plabel_cc_largest", "mixloss_fwd", "mixloss_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd", "norm_fwd", "norm_bwd", "gnorm_fwd", "gnorm_bwd", "norm_fwd_slabs", "norm_bwd_slabs", "conv3_fwd_raw", "conv3_dgrad_bwdstats", "pw16_bwd_norm_bwd", "conv3_c1_norm_bwd_wgrad", "conv3_pack_many",
              "conv3_fwd", "conv3_fwd_stats", "conv3_wgrad", "conv3_c1_fwd", "conv3_c1_fwd_stats", "conv3_c1_norm_fwd", "conv3_c1_norm_bwd", "conv3_c1_wgrad", "k2_pack_many", "down_fwd", "down_dgrad", "up_fwd", "k2_fwd_stats", "k2_dgrad_bwdstats", "up_fwd_norm", "up_norm_bwd",
              "up_dgrad", "pw_fwd", "k2_wgrad", "pw16_fwd", "pw16_bwd", "pw16_fwd_norm", "pw16_bwd_norm", "maxpool2d_fwd", "maxpool2d_bwd", "bilinear2x_fwd", "bilinear2x_bwd",
              "copy_channels", "ema", "sgd", "adam",

@@ -1,7 +1,8 @@
 """3-D V-Net on the MI355X kernels -- drop-in for the reference's networks/VNet.py:VNet (LA, BatchNorm3d +
-Dropout3d) and pancreas/Vnet.py:VNet (InstanceNorm3d, `branchs` head).
+Dropout3d) and pancreas/Vnet.py:VNet (InstanceNorm3d, `branchs` head), each also with normalization='groupnorm'
+(nn.GroupNorm(16, C) after every conv: networks/VNet.py:20-21, pancreas/Vnet.py:22-23).
 
-Same constructor arguments, same `state_dict()` keys / shapes (259 / 60), same `parameters()` order,
+Same constructor arguments, same `state_dict()` keys / shapes (259 / 60; groupnorm 172 / 118), same `parameters()` order,
 same call result: `(out_seg, features)` for the LA net, `[out]` for the pancreas net.  What differs is
 what runs: every layer is a call into libbcp_hip.so (NDHWC fp32, MFMA implicit-GEMM convs, fused
 norm+act(+dropout,+skip) streams), scheduled by `_forward_impl` / `_backward_impl` below; autograd
@@ -17,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip_ops as H
-from ._hipnet import BNP, ConvP, HipNet, Holder, NetFn, Seq, contrastive_heads
+from ._hipnet import BNP, GNP, ConvP, HipNet, Holder, NetFn, Seq, contrastive_heads
 
 
 class _Layer:
@@ -42,17 +43,19 @@ class VNet(HipNet):
         assert n_filters == 16 and not has_residual, "only the configuration the BCP scripts use is implemented"
         assert n_channels == 1, "the hot path is single-channel (LA / pancreas); see DESIGN.md"
         la = variant == "la"
+        gn = normalization == "groupnorm"
         if la:
-            assert normalization == "batchnorm", "networks/net_factory.py builds the LA V-Net with batchnorm"
+            assert normalization == "batchnorm" or gn, "networks/net_factory.py builds the LA V-Net with batchnorm"
         else:
-            assert normalization == "instancenorm"
+            assert normalization == "instancenorm" or gn
         self.variant = variant
         self.norm = normalization
+        self._gn = gn        # GroupNorm(16, C): per-sample statistics, no running buffers, train() and eval() one function
         self.has_dropout = has_dropout
         self.n_classes = n_classes
         nf = n_filters
         self._layers = []
-        bn = la
+        bn = la or gn
 
         def block(owner, name, n, cin, cout, kind="c3"):
             items = []
@@ -69,9 +72,10 @@ class VNet(HipNet):
                     fan = cout * 8
                 conv = ConvP(w, fan, cout)
                 items.append((3 * i, conv))
-                b = BNP(cout) if bn else None
+                b = (GNP(cout) if gn else BNP(cout)) if bn else None
                 if b is not None:
-                    b._live = True
+                    if not gn:
+                        b._live = True
                     items.append((3 * i + 1, b))
                 k = "c1" if (kind == "c3" and ci == 1) else kind
                 self._layers.append(_Layer(k, conv, b, ci, cout, f"{name}.{3 * i}"))
@@ -190,7 +194,11 @@ class VNet(HipNet):
         feat = None
         last = len(self._layers) - 1
         Ll = self._layers[last]
-        fuse_head = (self.fuse_head and self.training and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32)
+        gn = self._gn
+        # GroupNorm evaluates exactly as it trains: every kernel choice below that asks "training?" for the sake of batch statistics takes the
+        # training answer in both modes, so model.eval() gives the train-mode bits (dropout apart)
+        tr = self.training or gn
+        fuse_head = (self.fuse_head and tr and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32)
         for li, L in enumerate(self._layers):
             w, b = L.conv.weight, L.conv.bias
             part, nb = None, 0
@@ -199,17 +207,17 @@ class VNet(HipNet):
             # deep levels (<= 4096 rows per normalisation group) whose conv runs split-K: the conv leaves its raw slabs and the norm's
             # statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs) -- no slab-sum launch; decided per layer below
             sp = h.shape[1] * h.shape[2] * h.shape[3]
-            slabs_ok = (self.training and L.kind == "c3" and not (li == last and fuse_head) and ops.norm_slabs_ok(G, N * sp // G, L.cout))
+            slabs_ok = (self.training and not gn and L.kind == "c3" and not (li == last and fuse_head) and ops.norm_slabs_ok(G, N * sp // G, L.cout))
             small = False
             src, nsl, bsrc = None, 1, None
             fused_c1 = False
             fused_up = False
             if L.kind == "c1":
-                fused_c1 = (self.fuse_c1 and self.training and not small and not L.skip_pop and L.drop is None and not getattr(self, "_keep_saved", False)
+                fused_c1 = (self.fuse_c1 and self.training and not gn and not small and not L.skip_pop and L.drop is None and not getattr(self, "_keep_saved", False)
                             and not (li == last and fuse_head) and ops.conv3_c1_norm_ok(h.shape, 3, G))
                 if fused_c1:
                     y = None       # conv + norm + ReLU with recompute (bcp_conv3_c1_norm_fwd): the 16-channel pre-norm tensor is never written
-                elif self.training and not small:
+                elif tr and not small:
                     y, part, nb = ops.conv3_c1_fwd_stats(h, w.data, b.data, 3, G)      # statistics in the epilogue: no pass over the 16-channel y
                 else:
                     y = ops.conv3_c1_fwd(h, w.data, b.data, 3)
@@ -218,11 +226,11 @@ class VNet(HipNet):
                 sk = ops.conv3_nslabs(h.shape, L.cout, 3) if slabs_ok else 0
                 if sk > 1:
                     src, nsl, bsrc, small = ops.conv3_fwd_raw(h, wf, L.cout, 3, sk), sk, b.data, True
-                elif self.training or L.bn is None:
+                elif tr or L.bn is None:
                     y, part, nb = ops.conv3_fwd_stats(h, wf, b.data, L.cout, 3, G)
                 else:
                     y = ops.conv3_fwd(h, wf, b.data, L.cout, 3)          # eval-mode BatchNorm needs no batch statistics
-            elif (L.kind == "up" and self.training and L.drop is None and not (li == last and fuse_head) and not getattr(self, "_keep_saved", False)
+            elif (L.kind == "up" and self.training and not gn and L.drop is None and not (li == last and fuse_head) and not getattr(self, "_keep_saved", False)
                   and (not save or self.UP_RECOMPUTE_GRAD) and ops.up_norm_rows(h.shape, L.cout, G) > 0):
                 # (round 6) transposed conv + norm + ReLU + skip add with recompute (bcp_up_fwd_norm): the pre-norm tensor is never written
                 bp, _ = self.k2_packed(("k2", li), save)
@@ -231,7 +239,7 @@ class VNet(HipNet):
                 kind = 0 if L.kind == "dw" else 1
                 bp, _ = self.k2_packed(("k2", li), save)
                 # (round 6) the norm's statistics from the GEMM's epilogue where the shape has them: no statistics pass over y
-                if self.training and ops.k2_stat_rows(kind, h.shape, L.cout, G) > 0:       # (library option k2_stats = 0: never)
+                if tr and ops.k2_stat_rows(kind, h.shape, L.cout, G) > 0:       # (library option k2_stats = 0: never)
                     y, part, nb = ops.k2_fwd_stats(kind, h, bp, b.data, L.cout, G)
                 elif kind == 0:
                     y = ops.down_fwd(h, bp, b.data, L.cout)
@@ -252,6 +260,11 @@ class VNet(HipNet):
                 a, stats, y = ops.norm_fwd_slabs(src, nsl, bsrc, G,
                                                  *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4),
                                                  H.ACT_RELU, chan_scale=cs, residual=res)
+            elif gn:
+                # GroupNorm: statistics (the producer's rows, or a pass of its own) -> finalize -> apply; in front of the fused head the table only
+                head = li == last and fuse_head
+                a, stats = ops.gnorm_fwd(y, L.bn.weight.data, L.bn.bias.data, H.ACT_RELU, chan_scale=cs, residual=None if head else res,
+                                         partial=part, nb=nb, stats_only=head)
             elif li == last and fuse_head:
                 # the head normalises on its way in: block_nine's 16-channel activation is never written (statistics only here)
                 bn = L.bn
@@ -302,7 +315,7 @@ class VNet(HipNet):
         if h_last is None:
             Ll = self._layers[-1]
             _, y9, st9, cs9, _ = saved[len(self._layers) - 1]
-            if ops.HEAD_BWD_FUSED and not Ll.skip_pop:
+            if ops.HEAD_BWD_FUSED and not Ll.skip_pop and not self._gn:      # (the one-call form makes BatchNorm's backward coefficients itself)
                 dg9, db9 = (Ll.bn.weight.grad, Ll.bn.bias.grad) if Ll.bn is not None else (None, None)
                 dy_head = ops.pw16_bwd_norm_bwd(y9, st9, cs9, G, H.ACT_RELU, dlogits, self._out.weight.data, self._out.weight.grad,
                                                 self._out.bias.grad, dg9, db9, norm_accumulate=Ll.bn is not None, accumulate=True)
@@ -354,6 +367,10 @@ class VNet(HipNet):
                     self._grads_final_from(w, da)
                     break
                 dy = ops.conv3_c1_norm_bwd(x_in, w.data, L.conv.bias.data, 3, G, stats, da, H.ACT_RELU, dg, db, L.bn is not None)
+            elif self._gn:
+                # conv biases in front of GroupNorm layers with more than one channel per group receive their gradient (DESIGN.md "bias gradients")
+                dy = ops.gnorm_bwd(y, da, stats, L.bn.weight.data, H.ACT_RELU, dg, db, L.conv.bias.grad if L.cout > 16 else None, True,
+                                   chan_scale=cs, partial=bpart, nb=bnb)
             elif nsl > 1:
                 # deep levels: dh is the raw split-K slabs of the dgrad that produced it; the backward-statistics pass sums them (bcp_norm_bwd_slabs)
                 dy, da = ops.norm_bwd_slabs(y, da, nsl, G, stats, H.ACT_RELU, dg, db, L.bn is not None, chan_scale=cs)
@@ -363,8 +380,8 @@ class VNet(HipNet):
             if L.skip_pop:
                 skip_grads.append(da)       # d(out)/d(skip) = identity: the skip source gets `da` itself
             gw, acc = w.grad, True
-            # conv biases feed a norm: their gradient is identically zero (DESIGN.md "bias gradients"); the flat
-            # gradient buffer was cleared by begin_backward(), nothing to add.
+            # conv biases feed a norm: behind BatchNorm / InstanceNorm their gradient is identically zero (DESIGN.md "bias gradients"); the flat
+            # gradient buffer was cleared by begin_backward(), nothing to add.  (GroupNorm: gnorm_bwd above has added it.)
             # The weight gradient of a layer has no consumer inside the backward pass: it runs on a side stream underneath
             # the dgrad -> norm_bwd critical path (the deep levels' kernels are too small to fill 256 CUs on their own).
             # (round 6) every fork onto the side stream is an event record between two kernels of the MAIN stream -- a 5-7 us gap in front of
@@ -379,7 +396,7 @@ class VNet(HipNet):
                 _, wd = self.conv3_packed(("c3", li), True)
                 # the consumer of this dgrad is the previous layer's norm backward: at the deep levels it takes the raw split-K slabs
                 # (no slab-sum launch); the previous layer must have a pre-norm tensor of its own (not the recomputing first layer)
-                sk = (ops.conv3_nslabs(dy.shape, L.cin, 3) if li > 0 and saved[li - 1][1] is not None
+                sk = (ops.conv3_nslabs(dy.shape, L.cin, 3) if li > 0 and saved[li - 1][1] is not None and not self._gn
                       and ops.norm_slabs_ok(G, x_in.numel() // (L.cin * G), L.cin) else 0)
                 if sk > 1:
                     dh, nsl = ops.conv3_fwd_raw(dy, wd, L.cin, 3, sk), sk

@@ -36,6 +36,15 @@ class BNP(nn.Module):
         self.register_buffer("num_batches_tracked", torch.tensor(0, dtype=torch.long))
 
 
+class GNP(nn.Module):
+    """GroupNorm parameter holder (state_dict-compatible with nn.GroupNorm: weight = ones, bias = zeros, no buffers)"""
+
+    def __init__(self, c):
+        super().__init__()
+        self.weight = nn.Parameter(torch.ones(c))
+        self.bias = nn.Parameter(torch.zeros(c))
+
+
 class Seq(nn.Module):
     """numbered children, like nn.Sequential's naming (indices may have gaps for ReLU / Dropout slots)"""
 

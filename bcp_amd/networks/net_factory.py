@@ -7,14 +7,16 @@ def _dev():
     return torch.device("cuda", torch.cuda.current_device())
 
 
-def net_factory(net_type="unet", in_chns=1, class_num=2, mode="train", tsne=0):
+def net_factory(net_type="unet", in_chns=1, class_num=2, mode="train", tsne=0, normalization="batchnorm"):
+    """normalization: the V-Net's norm layers -- "batchnorm" (what the reference's factory builds) or "groupnorm" (nn.GroupNorm(16, C),
+    networks/VNet.py:20-21); the U-Net takes none"""
     if net_type == "unet" and mode == "train":
         from .unet import UNet
         net = UNet(in_chns=in_chns, class_num=class_num).to(_dev())
     elif net_type == "VNet" and mode == "train" and tsne == 0:
-        net = VNet(n_channels=in_chns, n_classes=class_num, normalization='batchnorm', has_dropout=True).to(_dev())
+        net = VNet(n_channels=in_chns, n_classes=class_num, normalization=normalization, has_dropout=True).to(_dev())
     elif net_type == "VNet" and mode == "test" and tsne == 0:
-        net = VNet(n_channels=in_chns, n_classes=class_num, normalization='batchnorm', has_dropout=False).to(_dev())
+        net = VNet(n_channels=in_chns, n_classes=class_num, normalization=normalization, has_dropout=False).to(_dev())
     else:
         raise NotImplementedError(f"net_factory({net_type!r}, mode={mode!r}): not on the BCP hot path (SURVEY.md section 2)")
     return net.flatten_()

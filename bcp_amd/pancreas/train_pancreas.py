@@ -147,6 +147,8 @@ def build_parser():
                          "Dice, Jaccard, 95HD, ASD) over the test split and log the four averages")
     ap.add_argument("--mask_strategy", type=str, default="box", choices=("box", "random", "concat"),
                     help="the copy-paste region: box = one 64^3 box (the reference's loop), random = 27 small boxes, concat = one slab along z (utils/BCP_utils.py:30-56)")
+    ap.add_argument("--normalization", type=str, default="instancenorm", choices=("instancenorm", "groupnorm"),
+                    help="the V-Net's norm layers: instancenorm (the reference's create_Vnet) or groupnorm = nn.GroupNorm(16, C) (pancreas/Vnet.py:22-23)")
     return ap
 
 
@@ -162,7 +164,7 @@ def main(argv=None):
     torch.manual_seed(seed_test)
     device = torch.device("cuda", torch.cuda.current_device())
     plan.use_real_stream(device)      # a real stream: what the capture of the recorded forward passes into HIP graphs needs (plan.GRAPHS = 1, the default)
-    net, ema_net = create_Vnet(), create_Vnet(ema=True)
+    net, ema_net = create_Vnet(normalization=args.normalization), create_Vnet(ema=True, normalization=args.normalization)
     net.volatile_io = ema_net.volatile_io = True      # the loops below consume a pass's outputs before the network's next pass (networks/_hipnet.py)
     ema_net.load_state_dict(net.state_dict())
     optimizer = train_step.FlatAdam(net, lr=lr)

@@ -30,7 +30,8 @@ def load_weights(net, path):
     ckpt = torch.load(path, map_location=device)
     if isinstance(ckpt, dict) and "net" in ckpt and isinstance(ckpt["net"], dict):
         ckpt = ckpt["net"]
-    net.load_state_dict(ckpt)
+    from ..pancreas.pancreas_utils import _from_ref_keys      # the pancreas driver writes the reference's nn.DataParallel keys (save_net)
+    net.load_state_dict(_from_ref_keys(ckpt))
     return net
 
 

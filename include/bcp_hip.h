@@ -42,7 +42,7 @@ enum { BCP_WG_DOWN = 0, BCP_WG_UP = 1, BCP_WG_PW = 2 };
 /* ABI revision = 100 * round + change counter.  Bumped whenever an exported signature changes; a binding must refuse a library whose
  * bcp_version() differs from the header it was written against (bcp_amd/_lib.py does: a stale in-tree .so then fails at load, not
  * with shifted arguments inside a launch). */
-#define BCP_ABI_VERSION 513
+#define BCP_ABI_VERSION 514
 int bcp_version(void);
 const char* bcp_last_error(void);
 /* process-wide tuning / test switches (the library never reads the environment): name = a field of bcp::Options
@@ -178,6 +178,32 @@ int bcp_norm_bwd(const float* y, const float* da, int G, long long rows_per_grou
 /* partial_in: (sum dz, sum dz*xhat) partials [G][nb_in][C][2] computed by the caller -- the statistics pass over (y, da) is
  * skipped (not available together with chan_scale / elem_mask).  Producer: bcp_conv3_dgrad_bwdstats (round 3: the epilogue of the
  * bf16-pipe dgrad kernels, where the extra vector work overlaps the matrix pipe). */
+
+/* ---- GroupNorm + activation (+Dropout3d channel scale, +residual): normalization='groupnorm' of both V-Net classes,
+ *      nn.GroupNorm(num_groups=16, num_channels=C) after every conv (networks/VNet.py:20-21,49-50,77-78,104-105,131-132,
+ *      pancreas/Vnet.py:22-23,46-47,73-74).  y = float[N][rows_per_sample][C], C a power of two in 16..256, groups = 16: a group is
+ *      C / 16 adjacent channels of ONE sample, statistics over its C / 16 * rows_per_sample values (biased variance), so the result of a
+ *      sample does not depend on the batch it came in, and there are no running statistics: training and evaluation are one function.
+ *      stats = float[5][N][C] {mean_g, rstd_g, scale = gamma_c * rstd_g, beta_c, mean_c - mean_g}: rows 0..3 are the table
+ *      bcp_norm_fwd leaves for G = N (mean and rstd repeated over a group's channels), so everything that READS such a table
+ *      (bcp_pw16_fwd_norm / bcp_pw16_bwd_norm, the *_dgrad_bwdstats epilogues) serves a GroupNorm layer unchanged.
+ *      Launches: statistics pass (bcp_norm_fwd's, one group per sample; skipped with partial_in = the double[N][nb_in][C][2] rows a
+ *      *_fwd_stats epilogue left for groups = N) -> finalize (per-channel fp64 sums, a group's channels added in channel order: no
+ *      atomics) -> apply pass (bcp_norm_fwd's; out = NULL: statistics only).  Backward: dy = scale_c dz - rstd_g (k1_g + xhat k2_g) with
+ *      k_g the group means of gamma_c * (sum dz, sum dz xhat)_c; dgamma / dbeta (nullable pair) and dbias summed over the samples in order.
+ *      dbias_or_null [C]: the gradient sum_voxels dy of the bias of the conv that produced y.  Behind BatchNorm / InstanceNorm it is
+ *      identically zero; behind GroupNorm the group mean removes only the MEAN of a group's biases, so for C / 16 > 1 it is a real
+ *      gradient.  It follows in closed form (fp64) from the sums the finalize holds: no pass over dy.  C = 16: exact zeros.
+ *      accumulate: dgamma / dbeta / dbias += instead of =.  partial_in (backward): (sum dz, sum dz * xhat) rows [N][nb_in][C][2] as
+ *      bcp_conv3_dgrad_bwdstats & co leave them for groups = N (not together with chan_scale).
+ *      BCP_EINVAL before any launch: null / misaligned pointers, C % groups != 0, groups != 16 or C / groups > 16, bcp_norm_fwd's extents. */
+size_t bcp_gnorm_workspace_bytes(int N, long long rows_per_sample, int C);
+int bcp_gnorm_fwd(const float* y, int N, long long rows_per_sample, int C, int groups, const float* gamma, const float* beta, float eps, int act,
+                  const float* chan_scale_or_null /* [N][C] */, const float* residual_or_null, float* stats, void* workspace,
+                  const double* partial_in_or_null, int nb_in, float* out_or_null, float* amax_out_or_null /* |max| slots of out */, void* stream);
+int bcp_gnorm_bwd(const float* y, const float* da, int N, long long rows_per_sample, int C, int groups, const float* stats, const float* gamma,
+                  int act, const float* chan_scale_or_null, float* dgamma, float* dbeta, float* dbias_or_null, int accumulate, void* workspace,
+                  const double* partial_in_or_null, int nb_in, float* dy, float* amax_out_or_null /* |max| slots of dy */, void* stream);
 
 /* Deep levels (rows_per_group <= 4096: the 128- / 256-channel levels of the V-Nets, the U-Net's deepest level --
  * networks/VNet.py:74-86,101-113 block_four .. block_six, networks/unet.py down4 / up1): the producing conv leaves its raw split-K

@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 OUT="$ROOT/tests/_emu/asan"
 mkdir -p "$OUT"
 CXX=/opt/rocm/lib/llvm/bin/clang++
-SRCS="api elementwise loss norm conv3 conv3b conv3bw gemm cc pool2d eval comm replay"
+SRCS="api elementwise loss norm gnorm conv3 conv3b conv3bw gemm cc pool2d eval comm replay"
 FLAGS="-x c++ -O1 -g -std=c++17 -fPIC -w -fsanitize=address -shared-libasan -fno-omit-frame-pointer -I $ROOT/tools/emu"
 OBJS=""
 for s in $SRCS; do
