@@ -46,6 +46,9 @@ parser.add_argument("--mask_strategy", type=str, default="box", choices=("box", 
 parser.add_argument("--normalization", type=str, default="batchnorm", choices=("batchnorm", "groupnorm"),
                     help="the V-Net's norm layers: batchnorm (the reference's command line) or groupnorm = nn.GroupNorm(16, C) (networks/VNet.py:20-21): "
                          "per-sample statistics, so the result does not depend on how the batch is cut across ranks")
+parser.add_argument("--has_residual", action="store_true",
+                    help="residual blocks (networks/VNet.py:35-65 ResidualConvBlock): every block adds its input in front of its last ReLU.  Same "
+                         "checkpoint keys as the plain net: read such a checkpoint with eval_LA --has_residual")
 parser.add_argument("--augment", action="store_true",
                     help="cases larger than the patch + the device-side RandomRotFlip / RandomCrop (dataloaders/dataset.py)")
 
@@ -143,7 +146,7 @@ class _BestModel:
 
 
 def pre_train(args, snapshot_path, device):
-    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
+    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization, has_residual=args.has_residual)
     db_train, sampler = _data(args, device)
     optimizer = _optimizer(args, model)
     model.train()
@@ -163,8 +166,8 @@ def pre_train(args, snapshot_path, device):
 
 
 def self_train(args, pre_snapshot_path, self_snapshot_path, device):
-    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
-    ema_model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization)
+    model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization, has_residual=args.has_residual)
+    ema_model = net_factory(net_type=args.model, in_chns=1, class_num=num_classes, mode="train", normalization=args.normalization, has_residual=args.has_residual)
     for p in ema_model.parameters():
         p.detach_()                     # the teacher never sees a gradient
     model.volatile_io = ema_model.volatile_io = True      # this loop consumes a pass's outputs before the network's next pass (networks/_hipnet.py)
@@ -206,6 +209,7 @@ def main(argv=None):
         os.makedirs(d, exist_ok=True)
     logging.basicConfig(level=logging.INFO, format="[%(asctime)s.%(msecs)03d] %(message)s", datefmt="%H:%M:%S", stream=sys.stdout)
     logging.info(str(args))
+    logging.info("V-Net blocks: %s (a checkpoint holds the same keys either way: evaluate it with the same setting)", "residual" if args.has_residual else "plain")
     pre_train(args, phase_dirs[0], device)
     self_train(args, phase_dirs[0], phase_dirs[1], device)
 

@@ -14,7 +14,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libbcp_hip.so")
 
-ABI_VERSION = 514     # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
+ABI_VERSION = 515     # include/bcp_hip.h BCP_ABI_VERSION: the revision these signatures were written against
 
 P = C.c_void_p
 I = C.c_int
@@ -59,6 +59,9 @@ _SIGS = {
     "bcp_norm_workspace_bytes": (SZ, [I, L, I]),
     "bcp_norm_fwd": (I, [P, I, L, I, P, P, P, P, F, F, I, P, L, P, F, P, F, P, P, P, P, I, P, L, P, P]),
     "bcp_norm_bwd": (I, [P, P, I, L, I, P, I, P, L, P, F, P, F, P, P, I, P, P, I, P, P, P]),
+    "bcp_norm_fwd_res": (I, [P, I, L, I, P, P, P, P, F, F, I, P, L, P, I, P, P, P, I, P, P, P]),
+    "bcp_norm_bwd_res": (I, [P, P, P, I, I, L, I, P, I, P, L, P, P, I, P, P, P, P, P]),
+    "bcp_norm_eval_res": (I, [P, L, I, P, P, P, P, F, I, P, I, P, P]),
     "bcp_gnorm_workspace_bytes": (SZ, [I, L, I]),
     "bcp_gnorm_fwd": (I, [P, I, L, I, I, P, P, F, I, P, P, P, P, P, I, P, P, P]),
     "bcp_gnorm_bwd": (I, [P, P, I, L, I, I, P, P, I, P, P, P, P, I, P, P, I, P, P, P]),

@@ -533,6 +533,56 @@ class Ops:
                     em_seed, em_keep, _p(dgamma), _p(dbeta), int(bool(accumulate)), _p(ws), _p(partial), int(nb), _p(out), _p(self._amax_slot(out, backward=True)), self.stream(y))
         return out
 
+    # ------------------------------------------------------------------ BatchNorm with a pre-activation residual (has_residual=True: the closing
+    # layer of a ResidualConvBlock, networks/VNet.py:35-65): a = act(z + r) [* chan_scale], r [N,D,H,W,C] or [N,D,H,W,1] broadcast
+    @staticmethod
+    def _res_channels(y, res):
+        if res is None or tuple(res.shape[:-1]) != tuple(y.shape[:-1]):
+            raise _lib.BcpError("pre-activation residual: a tensor of the activation's rows, C or 1 channels wide")
+        return int(res.shape[-1])
+
+    def norm_fwd_res(self, y, G, gamma, beta, rmean, rvar, act, res, out=None, chan_scale=None, momentum=0.1, eps=1e-5, partial=None, nb=0):
+        """y [N,D,H,W,C], res the block input -> (a, stats[5,G,C]) with a = act(norm(y) + res) [* chan_scale]; G, the running statistics and
+        partial / nb as norm_fwd"""
+        self._chk(y, gamma, beta, rmean, rvar, chan_scale, res, out)
+        N, Cc = y.shape[0], y.shape[-1]
+        rows = y.numel() // Cc
+        rpg, rps = rows // G, rows // N
+        ws = self.workspace("norm", self._ws_bytes("bcp_norm_workspace_bytes", G, rpg, Cc), y)
+        stats = torch.empty((5, G, Cc), dtype=torch.float32, device=y.device)
+        if out is None:
+            out = torch.empty_like(y)
+        amax = self._amax_slot(out)
+        self.b.call("bcp_norm_fwd_res", _p(y), G, rpg, Cc, _p(gamma), _p(beta), _p(rmean), _p(rvar), float(momentum), float(eps), act, _p(chan_scale),
+                    rps, _p(res), self._res_channels(y, res), _p(stats), _p(ws), _p(partial), int(nb), _p(out), _p(amax), self.stream(y))
+        return out, stats
+
+    def norm_bwd_res(self, y, da, res, G, stats, act, dgamma=None, dbeta=None, accumulate=False, chan_scale=None, want_dres=True, out=None):
+        """backward of norm_fwd_res: -> (dy, dres); dres = da * chan_scale * act'(z + res) is the gradient of the block input through the
+        shortcut (None with want_dres=False, and for a broadcast residual, whose gradient the library does not produce)"""
+        self._chk(y, da, res, stats, dgamma, dbeta, chan_scale, out)
+        N, Cc = y.shape[0], y.shape[-1]
+        rows = y.numel() // Cc
+        rpg, rps = rows // G, rows // N
+        ws = self.workspace("norm", self._ws_bytes("bcp_norm_workspace_bytes", G, rpg, Cc), y)
+        if out is None:
+            out = torch.empty_like(y)
+        rc = self._res_channels(y, res)
+        dres = torch.empty_like(y) if (want_dres and rc == Cc) else None
+        self.b.call("bcp_norm_bwd_res", _p(y), _p(da), _p(res), rc, G, rpg, Cc, _p(stats), act, _p(chan_scale), rps, _p(dgamma), _p(dbeta),
+                    int(bool(accumulate)), _p(ws), _p(out), _p(dres), _p(self._amax_slot(out, backward=True)), self.stream(y))
+        return out, dres
+
+    def norm_eval_res(self, y, gamma, beta, rmean, rvar, act, res, eps=1e-5, out=None):
+        """eval-mode BatchNorm (running statistics, no update) with the residual in front of the activation"""
+        self._chk(y, gamma, beta, rmean, rvar, res, out)
+        Cc = y.shape[-1]
+        if out is None:
+            out = torch.empty_like(y)
+        self.b.call("bcp_norm_eval_res", _p(y), y.numel() // Cc, Cc, _p(gamma), _p(beta), _p(rmean), _p(rvar), float(eps), act, _p(res),
+                    self._res_channels(y, res), _p(out), self.stream(y))
+        return out
+
     # ------------------------------------------------------------------ GroupNorm (nn.GroupNorm(16, C): normalization='groupnorm' of the V-Nets)
     GN_GROUPS = 16
 

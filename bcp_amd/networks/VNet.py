@@ -1,6 +1,8 @@
 """3-D V-Net on the MI355X kernels -- drop-in for the reference's networks/VNet.py:VNet (LA, BatchNorm3d +
 Dropout3d) and pancreas/Vnet.py:VNet (InstanceNorm3d, `branchs` head), each also with normalization='groupnorm'
-(nn.GroupNorm(16, C) after every conv: networks/VNet.py:20-21, pancreas/Vnet.py:22-23).
+(nn.GroupNorm(16, C) after every conv: networks/VNet.py:20-21, pancreas/Vnet.py:22-23).  The LA class with BatchNorm also takes
+has_residual=True (ResidualConvBlock, networks/VNet.py:35-65): the last 3x3x3 layer of every block adds the block's input in front of its
+ReLU (bcp_norm_fwd_res / _bwd_res / _eval_res); same parameters and keys as the plain net.
 
 Same constructor arguments, same `state_dict()` keys / shapes (259 / 60; groupnorm 172 / 118), same `parameters()` order,
 same call result: `(out_seg, features)` for the LA net, `[out]` for the pancreas net.  What differs is
@@ -21,14 +23,20 @@ from .. import hip_ops as H
 from ._hipnet import BNP, GNP, ConvP, HipNet, Holder, NetFn, Seq, contrastive_heads
 
 
+class UnsupportedConfiguration(NotImplementedError, AssertionError):
+    """a constructor combination that is not built (an AssertionError too: what the constructor raised for these before it had this class)"""
+
+
 class _Layer:
-    __slots__ = ("kind", "conv", "bn", "cin", "cout", "name", "skip_push", "skip_pop", "drop")
+    __slots__ = ("kind", "conv", "bn", "cin", "cout", "name", "skip_push", "skip_pop", "drop", "closing", "block_first")
 
     def __init__(self, kind, conv, bn, cin, cout, name):
         self.kind, self.conv, self.bn, self.cin, self.cout, self.name = kind, conv, bn, cin, cout, name
         self.skip_push = False   # the INPUT of this (dw) layer is a skip source
         self.skip_pop = False    # this (up) layer adds the matching skip after its ReLU
         self.drop = None         # 'x5' / 'x9': Dropout3d on this layer's output
+        self.closing = False     # has_residual: last 3x3x3 layer of a block -- the block's input is added in front of its ReLU
+        self.block_first = False  # has_residual: first 3x3x3 layer of a block -- its input is the block input the closing layer adds
 
 
 class VNet(HipNet):
@@ -40,7 +48,11 @@ class VNet(HipNet):
     def __init__(self, n_channels=3, n_classes=2, n_filters=16, normalization="none", has_dropout=False, has_residual=False,
                  variant="la"):
         super().__init__()
-        assert n_filters == 16 and not has_residual, "only the configuration the BCP scripts use is implemented"
+        assert n_filters == 16, "only the configuration the BCP scripts use is implemented"
+        if has_residual and variant != "la":
+            raise UnsupportedConfiguration("has_residual: the pancreas V-Net of the reference (pancreas/Vnet.py) has no residual blocks")
+        if has_residual and normalization != "batchnorm":
+            raise UnsupportedConfiguration("has_residual is built for normalization='batchnorm' only (residual blocks with GroupNorm are not)")
         assert n_channels == 1, "the hot path is single-channel (LA / pancreas); see DESIGN.md"
         la = variant == "la"
         gn = normalization == "groupnorm"
@@ -52,6 +64,7 @@ class VNet(HipNet):
         self.norm = normalization
         self._gn = gn        # GroupNorm(16, C): per-sample statistics, no running buffers, train() and eval() one function
         self.has_dropout = has_dropout
+        self.has_residual = bool(has_residual)      # ResidualConvBlock (networks/VNet.py:35-65): same parameters, same keys, another function
         self.n_classes = n_classes
         nf = n_filters
         self._layers = []
@@ -127,6 +140,13 @@ class VNet(HipNet):
             idx5 = max(i for i, L in enumerate(self._layers) if L.name.startswith("block_five."))
             self._layers[idx5].drop = "x5"
             self._layers[-1].drop = "x9"
+        if self.has_residual:
+            # a block = a maximal run of 3x3x3 layers with one block name; its last layer adds the block's input in front of the ReLU
+            for i, L in enumerate(self._layers):
+                if L.kind in ("c1", "c3"):
+                    blk = L.name.rsplit(".", 1)[0]
+                    L.block_first = i == 0 or self._layers[i - 1].name.rsplit(".", 1)[0] != blk
+                    L.closing = i == len(self._layers) - 1 or self._layers[i + 1].name.rsplit(".", 1)[0] != blk
         # parameters that take part in the optimiser: everything the forward pass touches
         ids = set()
         for L in self._layers:
@@ -198,22 +218,27 @@ class VNet(HipNet):
         # GroupNorm evaluates exactly as it trains: every kernel choice below that asks "training?" for the sake of batch statistics takes the
         # training answer in both modes, so model.eval() gives the train-mode bits (dropout apart)
         tr = self.training or gn
-        fuse_head = (self.fuse_head and tr and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32)
+        fuse_head = (self.fuse_head and tr and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32 and not Ll.closing)
+        r_in = None                      # has_residual: the input of the block being walked
         for li, L in enumerate(self._layers):
             w, b = L.conv.weight, L.conv.bias
             part, nb = None, 0
             if L.skip_push:
                 skips.append(h)
+            if L.block_first:
+                r_in = h
             # deep levels (<= 4096 rows per normalisation group) whose conv runs split-K: the conv leaves its raw slabs and the norm's
             # statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs) -- no slab-sum launch; decided per layer below
             sp = h.shape[1] * h.shape[2] * h.shape[3]
-            slabs_ok = (self.training and not gn and L.kind == "c3" and not (li == last and fuse_head) and ops.norm_slabs_ok(G, N * sp // G, L.cout))
+            # (a closing layer of a residual block takes no fusion that applies relu(z) itself: bcp_norm_fwd_res / _eval_res read a plain y)
+            slabs_ok = (self.training and not gn and L.kind == "c3" and not L.closing and not (li == last and fuse_head)
+                        and ops.norm_slabs_ok(G, N * sp // G, L.cout))
             small = False
             src, nsl, bsrc = None, 1, None
             fused_c1 = False
             fused_up = False
             if L.kind == "c1":
-                fused_c1 = (self.fuse_c1 and self.training and not gn and not small and not L.skip_pop and L.drop is None and not getattr(self, "_keep_saved", False)
+                fused_c1 = (self.fuse_c1 and self.training and not gn and not small and not L.skip_pop and L.drop is None and not L.closing and not getattr(self, "_keep_saved", False)
                             and not (li == last and fuse_head) and ops.conv3_c1_norm_ok(h.shape, 3, G))
                 if fused_c1:
                     y = None       # conv + norm + ReLU with recompute (bcp_conv3_c1_norm_fwd): the 16-channel pre-norm tensor is never written
@@ -247,7 +272,14 @@ class VNet(HipNet):
                     y = ops.up_fwd(h, bp, b.data, L.cout)
             res = skips.pop() if L.skip_pop else None
             cs = self._chan_scale(L, N, xcl.device)
-            if fused_up:
+            if L.closing:
+                bn = L.bn
+                if self.training:
+                    a, stats = ops.norm_fwd_res(y, G, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, H.ACT_RELU, r_in, chan_scale=cs,
+                                                partial=part, nb=nb)
+                else:
+                    a, stats = ops.norm_eval_res(y, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, H.ACT_RELU, r_in), None
+            elif fused_up:
                 bn = L.bn
                 a, stats = ops.up_fwd_norm(h, bp, b.data, L.cout, G, *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
                                                                       if bn is not None else (None,) * 4), H.ACT_RELU, residual=res)
@@ -279,7 +311,7 @@ class VNet(HipNet):
             else:
                 a, stats = ops.norm_fwd(y, G, None, None, None, None, H.ACT_RELU, chan_scale=cs, residual=res, partial=part, nb=nb)
             if save:
-                saved.append((h, y, stats, cs, G))
+                saved.append((h, y, stats, cs, G) + ((r_in,) if L.closing else ()))
             h = a
             if L.drop == "x5" and getattr(self, "_want_feat", False) and min(a.shape[1:4]) >= 3:
                 feat = ops.maxpool3d_k3s2_fwd(a)      # pool(features[4]): the reference's second return value (networks/VNet.py:286-290)
@@ -348,11 +380,16 @@ class VNet(HipNet):
         bpart, bnb = None, 0             # backward-statistics partials of THIS layer's norm, left by the dgrad that produced dh
         for li in range(len(self._layers) - 1, -1, -1):
             L = self._layers[li]
-            x_in, y, stats, cs, _ = saved[li]
+            x_in, y, stats, cs = saved[li][:4]
             w = L.conv.weight
             da = dh
             dg, db = (L.bn.weight.grad, L.bn.bias.grad) if L.bn is not None else (None, None)
-            if dy_head is not None:
+            if L.closing:
+                # g = da * chan_scale * [z + r > 0] feeds the norm backward and, as dres, the gradient of the block input (block_one's r is the
+                # network input: no dres)
+                assert nsl == 1 and bpart is None
+                dy, dres = ops.norm_bwd_res(y, da, saved[li][5], G, stats, H.ACT_RELU, dg, db, True, chan_scale=cs, want_dres=li > 0)
+            elif dy_head is not None:
                 dy, dy_head = dy_head, None
             elif y is None and L.kind == "up":     # (round 6) the recomputing transposed conv: y = up(x_in) again, inside both passes of the norm's backward
                 assert nsl == 1 and cs is None
@@ -396,11 +433,13 @@ class VNet(HipNet):
                 _, wd = self.conv3_packed(("c3", li), True)
                 # the consumer of this dgrad is the previous layer's norm backward: at the deep levels it takes the raw split-K slabs
                 # (no slab-sum launch); the previous layer must have a pre-norm tensor of its own (not the recomputing first layer)
-                sk = (ops.conv3_nslabs(dy.shape, L.cin, 3) if li > 0 and saved[li - 1][1] is not None and not self._gn
+                # (has_residual: the dgrad of a block's FIRST layer is joined with the shortcut's gradient below -- a plain tensor, and no
+                #  statistics of the layer in front taken from it before the join.  A 3x3x3 layer never faces a closing layer: that ends its block)
+                sk = (ops.conv3_nslabs(dy.shape, L.cin, 3) if li > 0 and saved[li - 1][1] is not None and not self._gn and not L.block_first
                       and ops.norm_slabs_ok(G, x_in.numel() // (L.cin * G), L.cin) else 0)
                 if sk > 1:
                     dh, nsl = ops.conv3_fwd_raw(dy, wd, L.cin, 3, sk), sk
-                elif li > 0 and saved[li - 1][3] is None and saved[li - 1][1] is not None:      # (a recomputing layer in front keeps no pre-norm tensor)
+                elif li > 0 and saved[li - 1][3] is None and saved[li - 1][1] is not None and not L.block_first:      # (a recomputing layer in front keeps no pre-norm tensor)
                     # conv -> conv edge without a dropout epilogue: the dgrad epilogue leaves the previous norm layer's backward statistics
                     # (bcp_conv3_dgrad_bwdstats; a plain dgrad when the shape is not served)
                     dh, bpart, bnb = ops.conv3_dgrad_bwdstats(dy, wd, L.cin, 3, saved[li - 1][1], saved[li - 1][2], H.ACT_RELU, G)
@@ -413,12 +452,20 @@ class VNet(HipNet):
                 # (round 6) the layer in front has a pre-norm tensor of its own and no dropout epilogue: this dgrad's epilogue leaves its norm's
                 # backward statistics (bcp_down_dgrad_bwdstats / bcp_up_dgrad_bwdstats) where the shape is served -- no k_col_partial<1> pass over (y, da)
                 prev = saved[li - 1] if li > 0 else None
-                if prev is not None and prev[1] is not None and prev[3] is None and ops.k2_bwdstat_rows(kind, dy.shape, L.cin, G) > 0:
+                # (the epilogue rebuilds the ReLU pattern of the layer in front from z alone: not behind the closing layer of a residual block)
+                if (prev is not None and prev[1] is not None and prev[3] is None and not self._layers[li - 1].closing
+                        and ops.k2_bwdstat_rows(kind, dy.shape, L.cin, G) > 0):
                     dh, bpart, bnb = ops.k2_dgrad_bwdstats(kind, dy, bp, L.cin, prev[1], prev[2], H.ACT_RELU, G, out=sg, accumulate=sg is not None)
                 elif kind == 0:
                     dh = ops.down_dgrad(dy, bp, L.cin, out=sg, accumulate=True)
                 else:
                     dh = ops.up_dgrad(dy, bp, L.cin)
+            if L.block_first and li > 0:
+                # the join: the block input's gradient = the first layer's dgrad + the shortcut's dres.  The joined tensor is what the layer in
+                # front consumes (and, behind an up layer, what skip_grads receives)
+                assert nsl == 1 and bpart is None
+                dh = ops.axpy(dh, dres, 1.0)
+                ops._no_amax(dh)
         flush_wgrads()
         self._join_wgrad_stream(dlogits)
         return None

@@ -42,7 +42,7 @@ enum { BCP_WG_DOWN = 0, BCP_WG_UP = 1, BCP_WG_PW = 2 };
 /* ABI revision = 100 * round + change counter.  Bumped whenever an exported signature changes; a binding must refuse a library whose
  * bcp_version() differs from the header it was written against (bcp_amd/_lib.py does: a stale in-tree .so then fails at load, not
  * with shifted arguments inside a launch). */
-#define BCP_ABI_VERSION 514
+#define BCP_ABI_VERSION 515
 int bcp_version(void);
 const char* bcp_last_error(void);
 /* process-wide tuning / test switches (the library never reads the environment): name = a field of bcp::Options
@@ -178,6 +178,27 @@ int bcp_norm_bwd(const float* y, const float* da, int G, long long rows_per_grou
 /* partial_in: (sum dz, sum dz*xhat) partials [G][nb_in][C][2] computed by the caller -- the statistics pass over (y, da) is
  * skipped (not available together with chan_scale / elem_mask).  Producer: bcp_conv3_dgrad_bwdstats (round 3: the epilogue of the
  * bf16-pipe dgrad kernels, where the extra vector work overlaps the matrix pipe). */
+
+/* ---- BatchNorm + activation with a PRE-activation residual (ABI 515): the closing layer of the reference's ResidualConvBlock
+ *      (networks/VNet.py:35-65, has_residual=True):  out = act((y - mean) * scale + beta + r) [* chan_scale].
+ *      res_pre = r, the block's input: float[G * rows_per_group][res_channels], res_channels = C, or 1 for a residual broadcast over the
+ *      channels (block_one: the 1-channel network input).  G, gamma / beta, the running statistics (updated group after group), stats,
+ *      chan_scale / rows_per_sample, partial_in / nb_in, amax_out and the workspace (bcp_norm_workspace_bytes) are bcp_norm_fwd's;
+ *      there is no elementwise dropout, no out_ld and no statistics-only mode.  Backward: g = da * chan_scale * act'(z + r) -- the
+ *      pattern of z + r, not of z; dy = scale * (g - mean(g) - xhat * mean(g * xhat)); dgamma / dbeta (+= with accumulate) as
+ *      bcp_norm_bwd; dres_or_null <- g, the gradient of r through the shortcut (res_channels = C only: the gradient of a broadcast
+ *      residual is not produced).  bcp_norm_eval_res: bcp_norm_eval (running statistics, no update) with the residual in front of the
+ *      activation.  BCP_EINVAL before any launch: null / misaligned pointers, a null residual, res_channels not in {1, C}, out = NULL
+ *      (statistics only) together with a residual, dres with res_channels = 1, bcp_norm_fwd's extents. */
+int bcp_norm_fwd_res(const float* y, int G, long long rows_per_group, int C, const float* gamma, const float* beta, float* running_mean,
+                     float* running_var, float momentum, float eps, int act, const float* chan_scale, long long rows_per_sample,
+                     const float* res_pre, int res_channels, float* stats, void* workspace, const double* partial_in_or_null, int nb_in,
+                     float* out, float* amax_out_or_null, void* stream);
+int bcp_norm_bwd_res(const float* y, const float* da, const float* res_pre, int res_channels, int G, long long rows_per_group, int C,
+                     const float* stats, int act, const float* chan_scale, long long rows_per_sample, float* dgamma, float* dbeta,
+                     int accumulate, void* workspace, float* dy, float* dres_or_null, float* amax_out_or_null, void* stream);
+int bcp_norm_eval_res(const float* y, long long rows, int C, const float* gamma_or_null, const float* beta_or_null, const float* running_mean,
+                      const float* running_var, float eps, int act, const float* res_pre, int res_channels, float* out, void* stream);
 
 /* ---- GroupNorm + activation (+Dropout3d channel scale, +residual): normalization='groupnorm' of both V-Net classes,
  *      nn.GroupNorm(num_groups=16, num_channels=C) after every conv (networks/VNet.py:20-21,49-50,77-78,104-105,131-132,

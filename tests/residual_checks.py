@@ -1,0 +1,591 @@
+"""Residual V-Net checks (has_residual=True of the LA V-Net): the kernels of bcp_amd/csrc/norm_res.hip against torch fp64 autograd on the
+CPU, an fp64 restatement of the residual forward against a fixture captured from the reference (tests/golden/vnet_la_residual_tiny.npz,
+tools/make_golden_residual.py), and the residual network, step, plans and drivers against that restatement.  Shared by
+tests/test_emu_residual.py (host simulator) and tests/test_gpu_residual.py (-m gpu).
+
+Tolerances are the project's own: forward kernel_checks.close's default (rtol 1e-4), backward rtol 2e-4 (gnorm_checks._check_case);
+network: check_vnet_golden_tiny's and check_vnet_pattern_grads' bounds; step: gnorm_checks.check_gn_step's."""
+import ctypes
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import kernel_checks as K
+from bcp_amd import hip_ops as H
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vnet_la_residual_tiny.npz")
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+# ------------------------------------------------------------------------------------------ kernels
+class _Case:
+    """one seeded closing layer: inputs drawn as gnorm_checks._Case draws them, the fp64 reference (autograd: G consecutive
+    F.batch_norm(training=True) calls, + r, ReLU, Dropout3d scale) and the device tensors"""
+
+    def __init__(self, rng, dev, N, Cc, sp, G=1, use_cs=False, bcast=False):
+        self.N, self.C, self.sp, self.G, self.dev = N, Cc, sp, G, dev
+        self.y = K.R(rng, N, Cc, *sp) * 1.7 + 0.4
+        self.gamma = torch.from_numpy(rng.uniform(0.5, 1.5, Cc).astype(np.float32))
+        self.beta = torch.from_numpy(rng.uniform(-0.3, 0.3, Cc).astype(np.float32))
+        self.cs = torch.from_numpy(((rng.random((N, Cc)) < 0.5) * 2.0).astype(np.float32)) if use_cs else None
+        self.res = K.R(rng, N, 1 if bcast else Cc, *sp)
+        self.da = K.R(rng, N, Cc, *sp)
+        self.rm0 = K.R(rng, Cc) * 0.1
+        self.rv0 = torch.from_numpy(rng.uniform(0.5, 1.5, Cc).astype(np.float32))
+        yd, rd = self.y.double().requires_grad_(True), self.res.double().requires_grad_(True)
+        gd, bd = self.gamma.double().requires_grad_(True), self.beta.double().requires_grad_(True)
+        rm, rv = self.rm0.double().clone(), self.rv0.double().clone()
+        n = N // G
+        t = torch.cat([F.batch_norm(yd[g * n:(g + 1) * n], rm, rv, gd, bd, True, 0.1, 1e-5) + rd[g * n:(g + 1) * n] for g in range(G)])
+        a = F.relu(t)
+        if self.cs is not None:
+            a = a * self.cs.double().view(N, Cc, 1, 1, 1)
+        a.backward(self.da.double())
+        self.a_ref, self.dy_ref, self.dg_ref, self.db_ref, self.dres_ref = a.detach(), yd.grad, gd.grad, bd.grad, rd.grad
+        self.rm_ref, self.rv_ref = rm, rv
+        self.ycl, self.dacl, self.rescl = K.to_cl(self.y).to(dev), K.to_cl(self.da).to(dev), K.to_cl(self.res).to(dev)
+        self.gd, self.bd = self.gamma.to(dev), self.beta.to(dev)
+        self.csd = None if self.cs is None else self.cs.to(dev)
+
+    def fwd(self, ops, **kw):
+        rm, rv = self.rm0.clone().to(self.dev), self.rv0.clone().to(self.dev)
+        a, stats = ops.norm_fwd_res(self.ycl, self.G, self.gd, self.bd, rm, rv, H.ACT_RELU, self.rescl, chan_scale=self.csd, **kw)
+        return a, stats, rm, rv
+
+    def bwd(self, ops, stats, dg=None, db=None, accumulate=False, **kw):
+        return ops.norm_bwd_res(self.ycl, self.dacl, self.rescl, self.G, stats, H.ACT_RELU, dg, db, accumulate, chan_scale=self.csd, **kw)
+
+
+def _check_case(ops, c, tag):
+    Cc, dev = c.C, c.dev
+    a, stats, rm, rv = c.fwd(ops)
+    K.close(K.from_cl(a), c.a_ref, msg=f"norm_fwd_res {tag}")
+    K.close(rm, c.rm_ref, msg=f"{tag} running mean after {c.G} group(s)")
+    K.close(rv, c.rv_ref, msg=f"{tag} running var after {c.G} group(s)")
+    assert H.amax_value(a._bcp_amax) == float(a.abs().max()), f"{tag}: |max| of a"
+    dg, db = (torch.full((Cc,), 7.0).to(dev) for _ in range(2))
+    dy, dres = c.bwd(ops, stats, dg, db, False)
+    K.close(K.from_cl(dy), c.dy_ref, rtol=2e-4, msg=f"norm_bwd_res dy {tag}")
+    K.close(dg, c.dg_ref, rtol=2e-4, msg=f"norm_bwd_res dgamma {tag}")
+    K.close(db, c.db_ref, rtol=2e-4, msg=f"norm_bwd_res dbeta {tag}")
+    assert H.amax_value(dy._bcp_amax) == float(dy.abs().max()), f"{tag}: |max| of dy"
+    if c.res.shape[1] == Cc:
+        K.close(K.from_cl(dres), c.dres_ref, rtol=2e-4, msg=f"norm_bwd_res dres {tag}")
+    else:
+        assert dres is None      # the gradient of a broadcast residual (the network input) is not produced
+    dy2, dres2 = c.bwd(ops, stats, dg, db, True)
+    assert torch.equal(_bits(dy2), _bits(dy)) and (dres is None or torch.equal(_bits(dres2), _bits(dres)))
+    K.close(dg, 2 * c.dg_ref, rtol=2e-4, msg=f"norm_bwd_res dgamma accumulate {tag}")
+    K.close(db, 2 * c.db_ref, rtol=2e-4, msg=f"norm_bwd_res dbeta accumulate {tag}")
+    # no parameter gradients, no dres asked for: dy alone, the same bits
+    dy3, none = c.bwd(ops, stats, want_dres=False)
+    assert none is None and torch.equal(_bits(dy3), _bits(dy))
+    return a, stats, dy
+
+
+WIDTH_CASES = ((3, 16, (3, 5, 7)), (3, 32, (3, 5, 7)), (3, 64, (3, 5, 7)), (3, 128, (3, 5, 7)), (3, 256, (1, 3, 5)))
+
+
+def check_res_widths(ops, dev):
+    """C = 16 .. 256 at N = 3 with ragged extents, one BatchNorm group"""
+    rng = np.random.default_rng(41)
+    for (N, Cc, sp) in WIDTH_CASES:
+        _check_case(ops, _Case(rng, dev, N, Cc, sp), f"C={Cc}")
+
+
+def check_res_grouped(ops, dev):
+    """grouped BatchNorm (G = 2: the step's two sub-batches in one launch): the running statistics after both groups, and the launch against
+    two separate G = 1 calls bit for bit"""
+    rng = np.random.default_rng(42)
+    for (N, Cc, sp, cs) in ((4, 16, (3, 5, 7), False), (4, 64, (3, 5, 7), True), (2, 256, (1, 3, 5), False), (4, 32, (3, 5, 7), False)):
+        c = _Case(rng, dev, N, Cc, sp, G=2, use_cs=cs)
+        a, stats, dy = _check_case(ops, c, f"G=2 C={Cc} cs={cs}")
+        rm, rv = c.rm0.clone().to(dev), c.rv0.clone().to(dev)
+        n = N // 2
+        for g in range(2):
+            sl = slice(g * n, (g + 1) * n)
+            a1, st1 = ops.norm_fwd_res(c.ycl[sl].contiguous(), 1, c.gd, c.bd, rm, rv, H.ACT_RELU, c.rescl[sl].contiguous(),
+                                       chan_scale=None if c.csd is None else c.csd[sl].contiguous())
+            assert torch.equal(_bits(a1), _bits(a[sl])) and torch.equal(_bits(st1[:, 0]), _bits(stats[:, g])), f"C={Cc}: group {g} != a call of its own"
+        _, _, rm2, rv2 = c.fwd(ops)
+        assert torch.equal(_bits(rm), _bits(rm2)) and torch.equal(_bits(rv), _bits(rv2)), f"C={Cc}: running statistics, grouped vs in turn"
+
+
+def check_res_epilogues(ops, dev):
+    """the 1-channel broadcast residual at C = 16 (block_one); the Dropout3d channel scale at C = 256 and C = 16 (block_five, block_nine);
+    more than one partial row per group (C = 16 at (12, 16, 11))"""
+    rng = np.random.default_rng(43)
+    for (N, Cc, sp, G, cs, bc) in ((3, 16, (3, 5, 7), 1, False, True), (4, 16, (3, 5, 7), 2, False, True), (3, 256, (1, 3, 5), 1, True, False),
+                                   (3, 16, (3, 5, 7), 1, True, False), (3, 16, (12, 16, 11), 1, False, False), (2, 16, (12, 16, 11), 2, True, True)):
+        _check_case(ops, _Case(rng, dev, N, Cc, sp, G, cs, bc), f"C={Cc} sp={sp} G={G} cs={cs} bcast={bc}")
+
+
+def check_res_partial_in(ops, dev):
+    """statistics from the partial rows bcp_conv3_fwd_stats leaves, against the entry point's own statistics pass and the reference"""
+    rng = np.random.default_rng(44)
+    for (N, Cin, Cout, sp, G) in ((2, 32, 32, (8, 12, 20), 1), (2, 16, 16, (6, 5, 9), 2)):
+        x = K.R(rng, N, Cin, *sp)
+        w = K.R(rng, Cout, Cin, 3, 3, 3) * 0.1
+        b = K.R(rng, Cout) * 0.1
+        r = K.to_cl(K.R(rng, N, Cout, *sp)).to(dev)
+        gamma = torch.from_numpy(rng.uniform(0.5, 1.5, Cout).astype(np.float32))
+        beta = torch.from_numpy(rng.uniform(-0.3, 0.3, Cout).astype(np.float32))
+        wf, _ = ops.conv3_pack(w.to(dev).contiguous(), 3)
+        y, part, rows = ops.conv3_fwd_stats(K.to_cl(x).to(dev), wf, b.to(dev), Cout, 3, G)
+        assert rows > 0, "these shapes must support fused statistics"
+        yd = K.from_cl(y).cpu().double()
+        n = N // G
+        z = torch.cat([F.batch_norm(yd[g * n:(g + 1) * n], None, None, gamma.double(), beta.double(), True, 0.1, 1e-5) for g in range(G)])
+        a_ref = F.relu(z + K.from_cl(r).cpu().double())
+        rms = []
+        for kw in (dict(partial=part, nb=rows), dict()):
+            rm, rv = torch.zeros(Cout).to(dev), torch.ones(Cout).to(dev)
+            a, st = ops.norm_fwd_res(y, G, gamma.to(dev), beta.to(dev), rm, rv, H.ACT_RELU, r, **kw)
+            K.close(K.from_cl(a), a_ref, msg=f"norm_fwd_res C={Cout} G={G} {'from the conv epilogue' if kw else 'own statistics'}")
+            assert H.amax_value(a._bcp_amax) == float(a.abs().max())
+            rms.append((rm, rv, st))
+        K.close(rms[0][0], rms[1][0], rtol=1e-6, msg="running mean, the two ways")
+        K.close(rms[0][1], rms[1][1], rtol=1e-6, msg="running var, the two ways")
+        K.close(rms[0][2][:4], rms[1][2][:4], rtol=1e-6, msg="the two tables")
+
+
+def check_res_eval_kernel(ops, dev):
+    """the eval entry against F.batch_norm(training=False) + residual + ReLU in fp64, both residual widths"""
+    rng = np.random.default_rng(45)
+    for (N, Cc, sp, bc) in ((3, 16, (3, 5, 7), True), (3, 16, (3, 5, 7), False), (2, 64, (3, 5, 7), False), (1, 256, (1, 3, 5), False)):
+        y = K.R(rng, N, Cc, *sp) * 1.7 + 0.4
+        r = K.R(rng, N, 1 if bc else Cc, *sp)
+        gamma = torch.from_numpy(rng.uniform(0.5, 1.5, Cc).astype(np.float32))
+        beta = torch.from_numpy(rng.uniform(-0.3, 0.3, Cc).astype(np.float32))
+        rm = K.R(rng, Cc) * 0.3 + 0.4
+        rv = torch.from_numpy(rng.uniform(0.5, 3.0, Cc).astype(np.float32))
+        ref = F.relu(F.batch_norm(y.double(), rm.double(), rv.double(), gamma.double(), beta.double(), False, 0.1, 1e-5) + r.double())
+        rmd, rvd = rm.clone().to(dev), rv.clone().to(dev)
+        a = ops.norm_eval_res(K.to_cl(y).to(dev), gamma.to(dev), beta.to(dev), rmd, rvd, H.ACT_RELU, K.to_cl(r).to(dev))
+        K.close(K.from_cl(a), ref, msg=f"norm_eval_res C={Cc} bcast={bc}")
+        assert torch.equal(rmd.cpu(), rm) and torch.equal(rvd.cpu(), rv), "eval mode must not update the running statistics"
+
+
+def check_res_refusals(binding):
+    """bad arguments are refused with BCP_EINVAL and a bcp_last_error() text before any launch (no device needed)"""
+    G, rows, Cc = 1, 8, 32
+    buf = (ctypes.c_ubyte * (1 << 16))()
+    base = (ctypes.addressof(buf) + 15) & ~15
+    y, out, stats, ws, res = base, base + 4096, base + 8192, base + 16384, base + 12288
+    lib = binding.cdll
+    fwd, bwd, ev, err = lib.bcp_norm_fwd_res, lib.bcp_norm_bwd_res, lib.bcp_norm_eval_res, lib.bcp_last_error
+    fl = ctypes.c_float
+
+    def f(y=y, G=G, rows=rows, C=Cc, res=res, rc=Cc, stats=stats, ws=ws, out=out, part=None, nb=0):
+        return fwd(y, G, ctypes.c_longlong(rows), C, None, None, None, None, fl(0.1), fl(1e-5), 1, None, ctypes.c_longlong(rows), res, rc, stats, ws, part, nb,
+                   out, None, None)
+
+    def g(y=y, G=G, rows=rows, C=Cc, res=res, rc=Cc, stats=stats, ws=ws, out=out + 2048, da=out, dres=None, dg=None):
+        return bwd(y, da, res, rc, G, ctypes.c_longlong(rows), C, stats, 1, None, ctypes.c_longlong(rows), dg, None, 0, ws, out, dres, None, None)
+
+    def e(y=y, G=G, rows=rows, C=Cc, res=res, rc=Cc, stats=stats, ws=ws, out=out):
+        return ev(y, ctypes.c_longlong(rows), C, None, None, stats, ws, fl(1e-5), 1, res, rc, out, None)      # (stats / ws stand in for the running statistics)
+    for call in (f, g, e):
+        assert call(y=None) == -1 and b"null" in err()
+        assert call(stats=None) == -1 and b"null" in err()
+        assert call(ws=None) == -1 and b"null" in err()
+        assert call(out=None) == -1 and (b"null" in err() or b"statistics-only" in err())
+        assert call(res=None) == -1 and b"null residual" in err()
+        assert call(y=y + 4) == -1 and b"alignment" in err()
+        assert call(res=res + 4) == -1 and b"alignment" in err()
+        assert call(res=res + 2, rc=1) == -1 and b"alignment" in err()
+        assert call(out=out + 2052) == -1 and b"alignment" in err()
+        for rc in (0, 2, 16, 64):
+            assert call(rc=rc) == -1 and b"res_channels" in err()
+        assert call(C=8) == -1 and b"unsupported" in err()
+        assert call(C=48) == -1 and b"unsupported" in err()
+        assert call(rows=0) == -1 and b"extents" in err()
+    assert f(G=0) == -1 and g(G=0) == -1 and b"extents" in err()
+    assert f(out=None) == -1 and b"statistics-only" in err()      # stats_only together with a residual
+    assert f(part=ws, nb=0) == -1 and b"partial_in" in err()
+    assert g(da=None) == -1 and b"null" in err()
+    assert g(dres=out + 4) == -1 and b"alignment" in err()
+    assert g(dres=out + 1024, rc=1) == -1 and b"broadcast" in err()
+    assert g(dg=out) == -1 and b"together" in err()
+    assert not any(buf), "a refused call must not write"
+
+
+# ------------------------------------------------------------------------------------------ the residual network
+import bcp_oracle as O  # noqa: E402
+import net_checks as NC  # noqa: E402
+from bcp_amd.utils import BCP_utils as BU  # noqa: E402
+
+NET_SHAPE = (32, 32, 16)
+SIX = (("grad_block_one_w", "encoder.block_one.conv.0.weight"), ("grad_block_nine_w", "decoder.block_nine.conv.0.weight"),
+       ("grad_eight_up_w", "decoder.block_eight_up.conv.0.weight"), ("grad_one_dw_w", "encoder.block_one_dw.conv.0.weight"),
+       ("grad_out_conv_w", "decoder.out_conv.weight"), ("grad_bn1_w", "encoder.block_one.conv.1.weight"))
+
+
+def _res_layers():
+    """(kind, key prefix, first 3x3x3 layer of its block?, closing layer of its block?) in execution order: a block is a maximal run of
+    3x3x3 layers under one block name"""
+    L = [(k, p) for k, p, _, _ in O.vnet_layers()] + [("c3", "decoder.block_nine.conv.0")]
+    blk = [p.rsplit(".conv.", 1)[0] for _, p in L]
+    return [(k, p, k == "c3" and (i == 0 or blk[i - 1] != blk[i]), k == "c3" and (i == len(L) - 1 or blk[i + 1] != blk[i])) for i, (k, p) in enumerate(L)]
+
+
+def res_vnet_forward(P, x, drop_masks=None, train=True, variant="la", has_dropout=True, act_masks=None):
+    """fp64 / fp32 restatement of the reference's VNet(normalization='batchnorm', has_residual=True) called as decoder(encoder(x)), with
+    oracle.vnet_forward's signature (tests that need the oracle's step functions patch it in) and its act_masks hook: one boolean tensor
+    per norm layer in execution order, the activation evaluated as t * mask -- for a closing layer t = norm(conv(h)) + r.
+    Every stage but a block's last: h = relu(norm(conv(h))); the last: h = relu(norm(conv(h)) + r), r the block's input (block_one: the
+    1-channel network input, broadcast); up layers add their skip behind the ReLU, and that sum is the next block's r; the two Dropout3d
+    sites multiply behind the closing ReLU of block_five / block_nine."""
+    assert variant == "la"
+    h, r, skips, n = x, None, [], 0
+    for kind, pre, first, closing in _res_layers():
+        w, b = P[pre + ".weight"], P[pre + ".bias"]
+        if kind == "dw":
+            skips.append(h)
+        if first:
+            r = h
+        y = F.conv3d(h, w, b, padding=1) if kind == "c3" else F.conv3d(h, w, b, stride=2) if kind == "dw" else F.conv_transpose3d(h, w, b, stride=2)
+        t = O._norm_act(y, P, O._next(pre), "batchnorm", train)
+        if closing:
+            t = t + r
+        if act_masks is not None:
+            h = t * act_masks[n].to(t.dtype)
+        else:
+            h = F.relu(t)
+        n += 1
+        if kind == "up":
+            h = h + skips.pop()
+        site = "x5" if pre.startswith("encoder.block_five.") else "x9" if pre.startswith("decoder.block_nine.") else None
+        if closing and site is not None and has_dropout and drop_masks is not None:
+            h = h * drop_masks[site].to(h.dtype).view(h.shape[0], -1, 1, 1, 1) * 2.0
+    return F.conv3d(h, P["decoder.out_conv.weight"], P["decoder.out_conv.bias"])
+
+
+def patch_oracle(monkeypatch):
+    monkeypatch.setattr(O, "vnet_forward", res_vnet_forward)
+
+
+def _fixture():
+    g = np.load(GOLDEN)
+    P = O.init_params(O.vnet_param_shapes(), seed=int(g["param_seed"]), random_affine=True)
+    dm = {"x5": torch.from_numpy(g["drop_x5"].astype(np.float32)), "x9": torch.from_numpy(g["drop_x9"].astype(np.float32))}
+    return g, P, torch.from_numpy(g["x"]), torch.from_numpy(g["tgt"].astype(np.int64)), dm
+
+
+def check_restatement_vs_fixture():
+    """res_vnet_forward in fp64 == the reference's residual V-Net (the fixture): logits, loss, the six gradient tensors, all 118 gradient
+    norms and the running statistics to 1e-9 absolute; and it is NOT the plain net (relative L2 of the logits 0.73 with the same weights)"""
+    g, P, x, tgt, dm = _fixture()
+    assert int(g["n_keys"]) == 259 and len(g["grad_names"]) == 118
+    Pd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in P.items()}
+    Q = O._with_grad(Pd, set(O.trainable_keys(Pd)))
+    out = res_vnet_forward(Q, x.double(), dm, True)
+    loss = O.sup_loss_la(out, tgt)
+    loss.backward()
+    assert float((out.detach() - torch.from_numpy(g["logits"])).abs().max()) <= 1e-9
+    assert abs(float(loss.detach()) - float(g["loss"])) <= 1e-9
+    for key, name in SIX:
+        assert float((Q[name].grad - torch.from_numpy(g[key])).abs().max()) <= 1e-9, name
+    for name, nrm in zip([str(n) for n in g["grad_names"]], g["grad_norms"]):
+        assert abs(float(Q[name].grad.norm()) - float(nrm)) <= 1e-9, name
+    for key, name in (("rm_block_one", "encoder.block_one.conv.1.running_mean"), ("rv_block_one", "encoder.block_one.conv.1.running_var"),
+                      ("rm_block_nine", "decoder.block_nine.conv.1.running_mean"), ("rv_block_nine", "decoder.block_nine.conv.1.running_var")):
+        assert float((Q[name] - torch.from_numpy(g[key])).abs().max()) <= 1e-9, name
+    for k in Q:      # conv biases in front of BatchNorm: an identically zero gradient, rounding noise in fp64
+        if NC.is_prenorm_bias(k, Q):
+            assert float(Q[k].grad.abs().max()) < 1e-12, k
+    with torch.no_grad():
+        plain = O.vnet_forward({k: v.detach() for k, v in Pd.items()}, x.double(), dm, True)
+    assert K.rel_l2(plain, out.detach()) > 0.5, "the residual restatement must not be the plain net"
+
+
+def make_res_vnet(P, dev, ops, variant="la", has_dropout=True):
+    """net_checks.make_vnet with has_residual=True"""
+    from bcp_amd.networks.VNet import VNet
+    assert variant == "la"
+    net = VNet(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=has_dropout, has_residual=True).to(dev)
+    NC.load_params(net, P).flatten_()
+    if dev.type == "cpu":
+        net.set_ops(ops)
+        BU.set_test_ops(ops)
+    net.train()
+    return net
+
+
+def check_res_keys(dev):
+    """259 state_dict keys with the plain net's names and shapes, the reference's parameters() order; what stays refused says so"""
+    import json
+
+    import pytest
+    from bcp_amd.networks.VNet import VNet
+    meta = json.load(open(os.path.join(os.path.dirname(GOLDEN), "meta.json")))
+    net = VNet(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True, has_residual=True).to(dev)
+    assert net.has_residual
+    sd = net.state_dict()
+    assert len(sd) == 259 and [[k, list(v.shape)] for k, v in sd.items()] == meta["vnet_la_keys"]
+    assert [n for n, _ in net.named_parameters()] == meta["vnet_la_param_names"]
+    closing = [L.name for L in net._layers if L.closing]
+    assert closing == ["block_one.0", "block_two.3", "block_three.6", "block_four.6", "block_five.6", "block_six.6", "block_seven.6", "block_eight.3",
+                       "block_nine.0"], closing
+    assert not any(L.closing or L.block_first for L in VNet(n_channels=1, n_classes=2, normalization="batchnorm")._layers)
+    with pytest.raises(NotImplementedError, match="GroupNorm"):
+        VNet(n_channels=1, n_classes=2, normalization="groupnorm", has_residual=True)
+    with pytest.raises(NotImplementedError, match="pancreas"):
+        VNet(n_channels=1, n_classes=2, normalization="instancenorm", has_residual=True, variant="pancreas")
+
+
+def check_res_golden_tiny(ops, dev):
+    """the residual network against the fixture captured from the reference: net_checks.check_vnet_golden_tiny's bounds"""
+    g, P, x, tgt, dm = _fixture()
+    net = make_res_vnet(P, dev, ops)
+    net.drop_masks = dm
+    out, _ = net(x.to(dev))
+    K.close(out, torch.from_numpy(g["logits"]), rtol=2e-4, msg="residual vnet logits")
+    loss = BU.sup_loss(out, tgt.to(dev))
+    assert abs(float(loss.detach()) - float(g["loss"])) < 1e-5, (float(loss.detach()), float(g["loss"]))
+    loss.backward()
+    params = dict(net.named_parameters())
+    for n_, nrm in zip([str(n) for n in g["grad_names"]], g["grad_norms"]):
+        gr = params[n_].grad
+        assert gr is not None, n_
+        l2 = float(gr.double().norm())
+        if NC.is_prenorm_bias(n_, params):
+            assert l2 <= 1e-6 and nrm < 1e-4, (n_, l2, nrm)
+            continue
+        assert abs(l2 - nrm) / max(nrm, 1e-12) < 3e-2, (n_, l2, nrm)
+    for key, name in SIX:
+        r = K.rel_l2(params[name].grad, torch.from_numpy(g[key]))
+        assert r < 3e-2, (name, r)
+    sd = net.state_dict()
+    for key, name in (("rm_block_one", "encoder.block_one.conv.1.running_mean"), ("rv_block_one", "encoder.block_one.conv.1.running_var"),
+                      ("rm_block_nine", "decoder.block_nine.conv.1.running_mean"), ("rv_block_nine", "decoder.block_nine.conv.1.running_var")):
+        K.close(sd[name], torch.from_numpy(g[key]), msg=name)
+    assert int(sd["encoder.block_one.conv.1.num_batches_tracked"]) == 1
+
+
+def _pattern(net, li, s):
+    """activation pattern of layer li from what the HIP forward saved; a closing layer's is z + r > 0, rebuilt from the saved y, the table
+    and the block input"""
+    y, stats, G = s[1], s[2], s[4]
+    N, C = y.shape[0], y.shape[-1]
+    st = stats.view(5, G, C)
+    gi = torch.arange(N, device=y.device) // (N // G)
+    shp = (N, 1, 1, 1, C)
+    z = (y - st[0][gi].view(shp)) * st[2][gi].view(shp) + st[3][gi].view(shp)
+    if net._layers[li].closing:
+        z = z + s[5]
+    return (z > 0).permute(0, 4, 1, 2, 3).cpu()
+
+
+def check_res_pattern_grads(ops, dev, seed=11, N=2, bound=1e-4):
+    """net_checks.check_vnet_pattern_grads for the residual net: every gradient tensor against the fp64 restatement linearised on the
+    activation pattern the HIP forward took"""
+    rng = np.random.default_rng(seed)
+    P = O.init_params(O.vnet_param_shapes(), seed=seed + 200, random_affine=True)
+    x = torch.from_numpy(rng.standard_normal((N, 1) + NET_SHAPE, dtype=np.float32))
+    tgt = torch.from_numpy(rng.integers(0, 2, (N,) + NET_SHAPE))
+    dm = {"x5": torch.from_numpy((rng.random((N, 256)) < 0.5).astype(np.float32)), "x9": torch.from_numpy((rng.random((N, 16)) < 0.5).astype(np.float32))}
+    net = make_res_vnet(P, dev, ops)
+    net.drop_masks = dm
+    net._keep_saved = True
+    out = net(x.to(dev))[0]
+    loss = BU.sup_loss(out, tgt.to(dev))
+    loss.backward()
+    saved = net._last_saved
+    masks = [_pattern(net, li, s) for li, s in enumerate(saved[:-1])]
+    Pd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in P.items()}
+    Q = O._with_grad(Pd, set(O.trainable_keys(Pd)))
+    o64 = res_vnet_forward(Q, x.double(), dm, True, act_masks=masks)
+    l64 = O.sup_loss_la(o64, tgt)
+    l64.backward()
+    assert K.rel_l2(out, o64.detach()) < 1e-4 and abs(float(loss.detach()) - float(l64.detach())) < 1e-5
+    params = dict(net.named_parameters())
+    worst, n = ("", 0.0), 0
+    for k in Q:
+        gref = getattr(Q[k], "grad", None)
+        if gref is None or NC.is_prenorm_bias(k, params) or float(gref.norm()) < 1e-9:
+            continue
+        r = K.rel_l2(params[k].grad, gref)
+        n += 1
+        if r > worst[1]:
+            worst = (k, r)
+        assert r < bound, (k, r)
+    assert n >= 25, n
+    return worst
+
+
+def _random_running(P, seed):
+    rng = np.random.default_rng(seed)
+    Q = {k: v.clone() for k, v in P.items()}
+    for k in Q:
+        if k.endswith("running_mean"):
+            Q[k] = torch.from_numpy(rng.normal(0.0, 0.2, tuple(Q[k].shape)).astype(np.float32))
+        elif k.endswith("running_var"):
+            Q[k] = torch.from_numpy(rng.uniform(0.5, 2.0, tuple(Q[k].shape)).astype(np.float32))
+    return Q
+
+
+def check_res_eval(ops, dev):
+    """model.eval() (running statistics, no update, no dropout) against the restatement with train=False"""
+    rng = np.random.default_rng(17)
+    P = _random_running(O.init_params(O.vnet_param_shapes(), seed=301, random_affine=True), 302)
+    net = make_res_vnet(P, dev, ops)
+    x = torch.from_numpy(rng.standard_normal((2, 1) + NET_SHAPE, dtype=np.float32))
+    net.eval()
+    with torch.no_grad():
+        oe = net(x.to(dev))[0].clone()
+        ref = res_vnet_forward({k: v.clone() for k, v in P.items()}, x, None, False, has_dropout=False)
+    K.close(oe, ref, rtol=2e-4, msg="residual eval forward")
+    sd = net.state_dict()
+    for k in sd:
+        if "running" in k:
+            assert torch.equal(sd[k].cpu(), P[k]), k
+
+
+def check_res_groups(ops, dev):
+    """the groups=2 forward (the step's two sub-batches in one call) equals two separate calls bit for bit: logits and running statistics"""
+    rng = np.random.default_rng(21)
+    P = O.init_params(O.vnet_param_shapes(), seed=77, random_affine=True)
+    x = torch.from_numpy(rng.standard_normal((2, 1) + NET_SHAPE, dtype=np.float32)).to(dev)
+    a, b = make_res_vnet(P, dev, ops), make_res_vnet(P, dev, ops)
+    with torch.no_grad():
+        oa = a(x, turnoff_drop=True, groups=2)[0].clone()
+        ob = torch.cat([b(x[i:i + 1], turnoff_drop=True)[0].clone() for i in range(2)])
+    assert torch.equal(_bits(oa), _bits(ob)), f"grouped logits != separate calls: max |d| {float((oa - ob).abs().max()):.3e}"
+    sa, sb = a.state_dict(), b.state_dict()
+    for k in sa:
+        if "running" in k and k.startswith(("encoder", "decoder")):
+            assert torch.equal(_bits(sa[k]), _bits(sb[k])), k
+
+
+def check_res_step(ops, dev, monkeypatch):
+    """one LA self-training step (gnorm_checks.check_gn_step's layout and bounds) against the oracle step with the residual forward"""
+    from bcp_amd import train_step
+    patch_oracle(monkeypatch)
+    rng = np.random.default_rng(5)
+    sub = 2
+    P = O.init_params(O.vnet_param_shapes(), seed=81, random_affine=True)
+    vol, lab = O.synth_la_batch(4 * sub, shape=NET_SHAPE, seed=82)
+    drops = {k: {"x5": torch.from_numpy((rng.random((sub, 256)) < 0.5).astype(np.float32)),
+                 "x9": torch.from_numpy((rng.random((sub, 16)) < 0.5).astype(np.float32))} for k in ("t_a", "t_b", "s_l", "s_u")}
+    box = (3, 5, 2, 21, 21, 10)
+    ro = O.la_self_train_step({k: v.clone() for k, v in P.items()}, {k: v.clone() for k, v in P.items()}, vol, lab, box, drops, sub)
+    model, ema = make_res_vnet(P, dev, ops), make_res_vnet(P, dev, ops)
+    for p in ema.parameters():
+        p.detach_()
+    r = train_step.la_self_train_step(model, ema, None, vol.to(dev), lab.to(dev), 2 * sub, box=box, drops=drops)
+    dl = abs(float(r["loss"]) - float(ro["loss"]))
+    dpl = int((r["plab_a"].cpu().float() != ro["plab_a"]).sum() + (r["plab_b"].cpu().float() != ro["plab_b"]).sum())
+    params = dict(model.named_parameters())
+    names = ("decoder.out_conv.weight", "decoder.block_nine.conv.0.weight", "encoder.block_one.conv.0.weight")
+    gerr = {k: K.rel_l2(params[k].grad, ro["grads"][k]) for k in names}
+    print(f"[residual step] |dloss| {dl:.2e}  pseudo-label voxels differing {dpl}  gradients {gerr}")
+    assert dl < 1e-5, (float(r["loss"]), float(ro["loss"]))
+    assert dpl <= 4, dpl
+    for k, e in gerr.items():
+        assert e < 3e-2, (k, e)
+    opt = train_step.FlatSGD(model, lr=0.01)
+    for _ in range(2):
+        r = train_step.la_self_train_step(model, ema, opt, vol.to(dev), lab.to(dev), 2 * sub, box=box, drops=drops)
+        assert bool(torch.isfinite(r["loss"]))
+
+
+def check_res_launch_plans(ops, dev, monkeypatch, **kw):
+    """net_checks.check_launch_plans with residual networks: recorded launch plans / graphs == the eager path, bit for bit"""
+    monkeypatch.setattr(NC, "make_vnet", make_res_vnet)
+    NC.check_launch_plans(ops, dev, cases=(("la", True),), **kw)
+
+
+# ------------------------------------------------------------------------------------------ routes
+class _Spy:
+    """an Ops stand-in that forwards every call and notes (name, arguments, keywords, result)"""
+
+    def __init__(self, ops):
+        object.__setattr__(self, "_ops", ops)
+        object.__setattr__(self, "log", [])
+
+    def __getattr__(self, name):
+        v = getattr(self._ops, name)
+        if not callable(v) or name.startswith("_") or name in ("stream", "workspace", "event", "profile_begin", "profile_end"):
+            return v
+
+        def call(*a, **k):
+            r = v(*a, **k)
+            self.log.append((name, a, k, r))
+            return r
+        return call
+
+    def __setattr__(self, name, value):
+        setattr(self._ops, name, value)
+
+
+NORM_FWD = ("norm_fwd", "norm_fwd_res", "norm_fwd_slabs", "conv3_c1_norm_fwd", "up_fwd_norm", "norm_eval", "norm_eval_res")
+NORM_BWD = ("norm_bwd", "norm_bwd_res", "norm_bwd_slabs", "conv3_c1_norm_bwd", "conv3_c1_norm_bwd_wgrad", "up_norm_bwd", "pw16_bwd_norm_bwd")
+
+
+def _routes(ops, dev, has_residual):
+    """per layer of one training forward / backward: (forward norm op [+ ':stats_only'], backward norm op [+ ':partial'], True when a
+    *_dgrad_bwdstats epilogue took this layer's backward statistics)"""
+    from bcp_amd.networks.VNet import VNet
+    rng = np.random.default_rng(3)
+    P = O.init_params(O.vnet_param_shapes(), seed=91, random_affine=True)
+    net = VNet(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True, has_residual=has_residual).to(dev)
+    NC.load_params(net, P).flatten_()
+    net.use_plans = False
+    spy = _Spy(ops)
+    net.set_ops(spy)
+    if dev.type == "cpu":
+        BU.set_test_ops(ops)
+    net.train()
+    x = torch.from_numpy(rng.standard_normal((2, 1) + NET_SHAPE, dtype=np.float32)).to(dev)
+    tgt = torch.from_numpy(rng.integers(0, 2, (2,) + NET_SHAPE)).to(dev)
+    BU.sup_loss(net(x)[0], tgt).backward()
+
+    def has(args, kw, ptr):
+        return any(isinstance(t, torch.Tensor) and t.data_ptr() == ptr for t in list(args) + list(kw.values()))
+    routes, stats_of = [], {}
+    for li, L in enumerate(net._layers):
+        gam, dgam = L.bn.weight.data.data_ptr(), L.bn.weight.grad.data_ptr()
+        fwd = [(n, k, r) for n, a, k, r in spy.log if n in NORM_FWD and has(a, k, gam)]
+        bwd = [(n, k) for n, a, k, r in spy.log if n in NORM_BWD and has(a, k, dgam)]
+        assert len(fwd) == 1 and len(bwd) == 1, (L.name, [f[0] for f in fwd], [b[0] for b in bwd])
+        stats = fwd[0][2][1]
+        stats_of[li] = stats.data_ptr()
+        routes.append([fwd[0][0] + (":stats_only" if fwd[0][1].get("stats_only") else ""), bwd[0][0] + (":partial" if bwd[0][1].get("partial") is not None else ""), False])
+    for n, a, k, r in spy.log:
+        if n.endswith("_dgrad_bwdstats") and r[2] > 0:
+            hit = [li for li, p in stats_of.items() if has(a, k, p)]
+            assert len(hit) == 1, (n, hit)
+            routes[hit[0]][2] = True
+    head = [n for n, a, k, r in spy.log if n.startswith("pw16_")]
+    return net, routes, head
+
+
+def check_res_routes(ops, dev):
+    """walking the layer list of a residual net: no closing layer takes the fused first layer, the fused head, a slab route, or sits in
+    front of a *_dgrad_bwdstats epilogue; every non-closing layer takes the route it takes in the plain net -- but for the backward feed of
+    the dw / up layer in front of a block, whose gradient is joined with the shortcut's behind the block's first dgrad (a plain tensor: no
+    raw slabs, no statistics taken in front of the join)"""
+    net, res, head = _routes(ops, dev, True)
+    _, plain, phead = _routes(ops, dev, False)
+    assert "pw16_fwd_norm" in phead and "pw16_fwd_norm" not in head and "pw16_fwd" in head, (head, phead)      # the fused head is off: block_nine closes a block
+    assert any(p[0].startswith("conv3_c1_norm_fwd") for p in plain) or dev.type == "cpu"
+    nclosing = 0
+    for li, L in enumerate(net._layers):
+        r, p = res[li], plain[li]
+        if L.closing:
+            nclosing += 1
+            assert r == ["norm_fwd_res", "norm_bwd_res", False], (L.name, r)
+            continue
+        assert r[0] == p[0], (L.name, "forward route", r, p)
+        if li + 1 < len(net._layers) and net._layers[li + 1].block_first:
+            assert r[1] in ("norm_bwd", "up_norm_bwd") and not r[2], (L.name, "in front of a join", r)
+        else:
+            assert r[1:] == p[1:], (L.name, "backward route", r, p)
+    assert nclosing == 9
+    return res, plain
