@@ -1208,6 +1208,7 @@ _PROFILED = ("mix_box", "plabel_bin", "plabel_argmax4", "cc_largest", "plabel_cc
              "conv3_fwd", "conv3_fwd_stats", "conv3_wgrad", "conv3_c1_fwd", "conv3_c1_fwd_stats", "conv3_c1_norm_fwd", "conv3_c1_norm_bwd", "conv3_c1_wgrad", "k2_pack_many", "down_fwd", "down_dgrad", "up_fwd", "k2_fwd_stats", "k2_dgrad_bwdstats", "up_fwd_norm", "up_norm_bwd",
              "up_dgrad", "pw_fwd", "k2_wgrad", "pw16_fwd", "pw16_bwd", "pw16_fwd_norm", "pw16_bwd_norm", "maxpool2d_fwd", "maxpool2d_bwd", "bilinear2x_fwd", "bilinear2x_bwd",
              "copy_channels", "ema", "sgd", "adam",
+             "norm_fwd_res", "norm_bwd_res", "norm_eval_res", "axpy",              # has_residual=True: the closing layers' norms and the shortcut join
              "norm_eval", "sw_accumulate", "sw_finish", "overlap_counts")      # the validation passes (eager: never inside a recorded pass)
 
 

@@ -4,7 +4,9 @@ tools/make_golden_residual.py), and the residual network, step, plans and driver
 tests/test_emu_residual.py (host simulator) and tests/test_gpu_residual.py (-m gpu).
 
 Tolerances are the project's own: forward kernel_checks.close's default (rtol 1e-4), backward rtol 2e-4 (gnorm_checks._check_case);
-network: check_vnet_golden_tiny's and check_vnet_pattern_grads' bounds; step: gnorm_checks.check_gn_step's."""
+network: check_vnet_golden_tiny's and check_vnet_pattern_grads' bounds; step: gnorm_checks.check_gn_step's.  The check_edge_* cases hold every
+element to tests/product_ops.py's bounds instead (|out - ref64| <= tau * cond) at the smallest shapes that reach the loops and branches
+of norm_res.hip the cases above leave out; all of them run on the simulator and on the device."""
 import ctypes
 import os
 
@@ -213,6 +215,171 @@ def check_res_refusals(binding):
     assert g(dres=out + 1024, rc=1) == -1 and b"broadcast" in err()
     assert g(dg=out) == -1 and b"together" in err()
     assert not any(buf), "a refused call must not write"
+
+
+# ------------------------------------------------------------------------------------------ loop and branch edges, element by element
+# The cases above hold whole tensors to max-scaled bounds (K.close).  The cases below run the loops and branches of csrc/norm_res.hip that
+# those shapes never reach, and hold every element to tests/product_ops.py's bounds (check_elementwise: |out - ref64| <= tau * cond) with
+# its fp64 references: TAU for a / dy / dgamma / dbeta, TAU_DRES for dres, TAU_NORM_EVAL for the eval entry; kink elements capped at
+# KINK_CAP on the reference alone.
+import time  # noqa: E402
+
+import product_ops as P  # noqa: E402
+
+
+class _Ew:
+    """one closing layer on product_ops' input generators: inputs, fp64 references (computed once), and run() -- the device launches alone"""
+
+    def __init__(self, ops, dev, seed, ys, G, flags, act=H.ACT_RELU):
+        self.dev, self.ys, self.G, self.flags, self.act = dev, tuple(ys), G, tuple(flags), act
+        g = torch.Generator().manual_seed(seed)
+        N, C = ys[0], ys[-1]
+        self.yd, self.y, self.part, self.rows, self.res = P._res_source(ops, dev, g, self.ys, G, self.flags)
+        self.gam, self.bet, self.rm0, self.rv0, self.cs = P._res_params(g, C, N, self.flags)
+        self.da = P.gradient(g, self.ys)
+        self.dg0, self.db0 = torch.randn(C, generator=g) * 1e-2, torch.randn(C, generator=g) * 1e-2
+        self.fwd_ref = P.res_fwd_ref64(self.y, G, self.gam, self.bet, act, self.res, self.cs)
+        self.bwd_ref = P.res_bwd_ref64(self.y, G, self.gam, self.bet, act, self.res, self.cs, self.da)
+        self.share = self.bwd_ref[-1]
+        P.KINK_SHARES.append((f"{self.ys} {self.flags}", self.share))
+        assert self.share <= P.KINK_CAP, f"{self.ys} {self.flags}: {self.share:.2e} of the elements at the kink (cap {P.KINK_CAP:.0e})"
+        self.resd, self.dad = self.res.to(dev), self.da.to(dev)
+        self.csd = None if self.cs is None else self.cs.to(dev)
+
+    def run(self, ops, partial=True, backward=True):
+        dev = self.dev
+        rm, rv = self.rm0.clone().to(dev), self.rv0.clone().to(dev)
+        kw = dict(partial=self.part, nb=self.rows) if (partial and self.rows) else {}
+        a, st = ops.norm_fwd_res(self.yd, self.G, self.gam.to(dev), self.bet.to(dev), rm, rv, self.act, self.resd, chan_scale=self.csd, **kw)
+        r = dict(a=a, st=st, rm=rm, rv=rv)
+        if backward:
+            dg, db = self.dg0.clone().to(dev), self.db0.clone().to(dev)
+            dy, dres = ops.norm_bwd_res(self.yd, self.dad, self.resd, self.G, st, self.act, dg, db, True, chan_scale=self.csd)
+            r.update(dy=dy, dres=dres, dg=dg, db=db)
+        return r
+
+    def check(self, r, tag):
+        """-> the worst error / bound ratio of a, dy, dres"""
+        C = self.ys[-1]
+        ref, cond, mu, var = self.fwd_ref
+        P._stats_check(r["st"], mu, var, tag)
+        worst = {"a": P.check_elementwise(r["a"].cpu(), ref, cond, P.TAU, tag + " a")[0]}
+        P._running_check(tag, r["rm"], r["rv"], self.rm0, self.rv0, mu, var, self.y.numel() // C // self.G)
+        assert H.amax_value(r["a"]._bcp_amax) == float(r["a"].abs().max()), f"{tag}: |max| of a"
+        if "dy" in r:
+            dref, dcond, dres_ref, dres_cond, dz, xg, dk, _ = self.bwd_ref
+            worst["dy"] = P.check_elementwise(r["dy"].cpu(), dref, dcond, P.TAU, tag + " dy")[0]
+            P._dgamma_dbeta_check(tag, r["dg"], r["db"], self.dg0, self.db0, dz, xg, dk)
+            if self.res.shape[-1] == C:
+                worst["dres"] = P.check_elementwise(r["dres"].cpu(), dres_ref, dres_cond, P.TAU_DRES, tag + " dres")[0]
+            else:
+                assert r["dres"] is None
+        return worst
+
+    @staticmethod
+    def same_bits(r0, r1, tag):
+        for k in r0:
+            if r0[k] is not None:
+                assert torch.equal(_bits(r0[k]), _bits(r1[k])), f"{tag}: {k} changed its bits"
+
+
+def _report(name, worst, t0):
+    print(f"[residual-edge] {name:44s} worst err/bound " + "  ".join(f"{k} {v:.3e}" for k, v in worst.items()) + f"  ({time.perf_counter() - t0:.1f} s)")
+
+
+def _merge(w, v):
+    for k, x in v.items():
+        w[k] = max(w.get(k, 0.0), x)
+    return w
+
+
+def check_edge_apply_wrap_option(ops, dev):
+    """the apply passes' grid-stride loop (k_norm_apply_res / k_norm_bwd_apply_res: row-reversed, unrolled by four, then a remainder loop):
+    with norm_apply_cap = 2 a launch has one or two workgroups, so every thread makes many unrolled trips and remainder trips -- with and
+    without the channel scale, full and broadcast residual, forward and backward, at C = 16 and C = 256.  Bit for bit the default
+    launch's results, and within the elementwise bounds"""
+    t0, worst = time.perf_counter(), {}
+    for (N, Cc, sp) in ((3, 16, (12, 16, 11)), (3, 256, (3, 5, 7))):
+        for cs in (False, True):
+            for bc in (False, True):
+                flags = (("chan_scale",) if cs else ()) + (("bcast",) if bc else ())
+                tag = f"apply cap 2: C={Cc} {flags}"
+                c = _Ew(ops, dev, 50 + Cc + 2 * cs + bc, (N,) + sp + (Cc,), 1, flags)
+                r0 = c.run(ops)
+                try:
+                    ops.set_option("norm_apply_cap", "2")
+                    r1 = c.run(ops)
+                finally:
+                    ops.set_option("norm_apply_cap", "")
+                _Ew.same_bits(r0, r1, tag)
+                _merge(worst, c.check(r1, tag))
+    _report("apply-pass wrap (norm_apply_cap = 2)", worst, t0)
+    return worst
+
+
+def check_edge_apply_wrap_default(ops, dev):
+    """the same loops at the library's own cap: N = 4, G = 2, C = 16 with a channel scale at (52, 52, 50) -- 135 200 rows per sample in
+    nseg = 4 segments, 540 800 float4 each against 512 workgroups x 256 threads x 4: one unrolled trip, then remainder trips"""
+    t0 = time.perf_counter()
+    c = _Ew(ops, dev, 61, (4, 52, 52, 50, 16), 2, ("chan_scale",))
+    worst = c.check(c.run(ops), "apply wrap at the default cap")
+    _report("apply-pass wrap (default cap, 4x52x52x50x16)", worst, t0)
+    return worst
+
+
+def check_edge_eval_wrap(ops, dev):
+    """k_norm_eval_res past its cap of 4096 workgroups: C = 16, N = 1, (66, 64, 63) = 1 064 448 float4 against 1 048 576 -- the second trip
+    of its loop, both residual widths"""
+    t0, worst = time.perf_counter(), {}
+    g = torch.Generator().manual_seed(62)
+    for flags in ((), ("bcast",)):
+        key = ("norm_eval_res", ((1, 66, 64, 63, 16), (16,), (16,)), (H.ACT_RELU,), 0)
+        _merge(worst, {"eval": P.drive_norm_eval_res(ops, dev, key, g, (flags,))[0][1][0]})
+    _report("eval wrap (1x66x64x63x16)", worst, t0)
+    return worst
+
+
+def check_edge_wide(ops, dev):
+    """C = 512 and C = 1024 (check_res_args accepts them; the cross-wave reduce of k_col_partial_res walks red[w][col & 63] with wpr = 2
+    and wpr = 4 there): N = 3, G = 1 and N = 4, G = 2 with a channel scale at (1, 3, 5); forward, backward and eval"""
+    t0, worst = time.perf_counter(), {}
+    g = torch.Generator().manual_seed(63)
+    for Cc in (512, 1024):
+        for (N, G, flags) in ((3, 1, ()), (4, 2, ("chan_scale",))):
+            c = _Ew(ops, dev, 64 + Cc + N, (N, 1, 3, 5, Cc), G, flags)
+            _merge(worst, c.check(c.run(ops), f"C={Cc} N={N} G={G} {flags}"))
+            key = ("norm_eval_res", ((N, 1, 3, 5, Cc), (Cc,), (Cc,)), (H.ACT_RELU,), 0)
+            _merge(worst, {"eval": P.drive_norm_eval_res(ops, dev, key, g, ((),))[0][1][0]})
+    _report("C = 512 / 1024", worst, t0)
+    return worst
+
+
+def check_edge_spg2_nbps2(ops, dev):
+    """a group of two samples (spg = 2) with two statistics blocks per sample (nbps = 2): N = 4, G = 2, C = 16, (12, 16, 11) with a channel
+    scale -- both factors of the partial-row index of k_col_partial_res above 1"""
+    t0 = time.perf_counter()
+    c = _Ew(ops, dev, 65, (4, 12, 16, 11, 16), 2, ("chan_scale",))
+    worst = c.check(c.run(ops), "spg=2 nbps=2")
+    _report("spg = 2 with nbps = 2", worst, t0)
+    return worst
+
+
+def check_edge_block_one_route(ops, dev):
+    """block_one's route: the statistics rows of a real conv3_c1_fwd_stats launch feed norm_fwd_res, the launch's 1-channel input is the
+    broadcast residual; G = 1 and G = 2.  The first-layer epilogue leaves rows at every extent (whole samples per group): (3, 5, 7), ragged
+    against its tiles.  Against the call's own statistics pass (K.close at 1e-6, as check_res_partial_in) and against fp64"""
+    t0, worst = time.perf_counter(), {}
+    for (N, G) in ((3, 1), (4, 2)):
+        c = _Ew(ops, dev, 66 + G, (N, 3, 5, 7, 16), G, ("partial", "bcast"))
+        assert c.rows > 0, "conv3_c1_fwd_stats must leave statistics rows here"
+        r0, r1 = c.run(ops), c.run(ops, partial=False, backward=False)
+        _merge(worst, c.check(r0, f"block_one route G={G}"))
+        _merge(worst, {"a (own statistics)": c.check(r1, f"block_one route G={G}, own statistics pass")["a"]})
+        K.close(r0["rm"], r1["rm"], rtol=1e-6, msg="running mean, the two ways")
+        K.close(r0["rv"], r1["rv"], rtol=1e-6, msg="running var, the two ways")
+        K.close(r0["st"][:4], r1["st"][:4], rtol=1e-6, msg="the two tables")
+    _report("block_one route (conv3_c1_fwd_stats rows)", worst, t0)
+    return worst
 
 
 # ------------------------------------------------------------------------------------------ the residual network

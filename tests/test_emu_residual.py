@@ -57,6 +57,31 @@ def test_res_refusals_product_library():
     R.check_res_refusals(_lib.Binding(_lib.LIB_PATH))
 
 
+# ---- loop and branch edges of csrc/norm_res.hip, element by element against fp64 (tests/product_ops.py's references and bounds)
+def test_edge_apply_wrap_option(emu_ops):
+    R.check_edge_apply_wrap_option(emu_ops, CPU)
+
+
+def test_edge_apply_wrap_default(emu_ops):
+    R.check_edge_apply_wrap_default(emu_ops, CPU)
+
+
+def test_edge_eval_wrap(emu_ops):
+    R.check_edge_eval_wrap(emu_ops, CPU)
+
+
+def test_edge_wide(emu_ops):
+    R.check_edge_wide(emu_ops, CPU)
+
+
+def test_edge_spg2_nbps2(emu_ops):
+    R.check_edge_spg2_nbps2(emu_ops, CPU)
+
+
+def test_edge_block_one_route(emu_ops):
+    R.check_edge_block_one_route(emu_ops, CPU)
+
+
 # ---- the fixture and the restatement (torch fp64 on the CPU only)
 def test_restatement_equals_reference_fixture():
     R.check_restatement_vs_fixture()

@@ -46,6 +46,31 @@ def test_res_refusals(gpu_ops):
     R.check_res_refusals(gpu_ops.b)
 
 
+# ---- loop and branch edges of csrc/norm_res.hip, element by element against fp64 (tests/product_ops.py's references and bounds)
+def test_edge_apply_wrap_option(gpu_ops, dev):
+    R.check_edge_apply_wrap_option(gpu_ops, dev)
+
+
+def test_edge_apply_wrap_default(gpu_ops, dev):
+    R.check_edge_apply_wrap_default(gpu_ops, dev)
+
+
+def test_edge_eval_wrap(gpu_ops, dev):
+    R.check_edge_eval_wrap(gpu_ops, dev)
+
+
+def test_edge_wide(gpu_ops, dev):
+    R.check_edge_wide(gpu_ops, dev)
+
+
+def test_edge_spg2_nbps2(gpu_ops, dev):
+    R.check_edge_spg2_nbps2(gpu_ops, dev)
+
+
+def test_edge_block_one_route(gpu_ops, dev):
+    R.check_edge_block_one_route(gpu_ops, dev)
+
+
 # ---- network
 def test_res_keys(dev):
     R.check_res_keys(dev)

@@ -64,13 +64,13 @@ def _reduced_rows():
     return rows
 
 
-# the LA rows (self-training, pre-training, validation) run in the default CPU suite; the pancreas / ACDC / batch-8 rows (same drivers,
-# other shapes) with BCP_EXTENDED=1.
+# the LA rows (self-training, pre-training, validation; plain and residual V-Net) run in the default CPU suite; the pancreas / ACDC /
+# batch-8 rows (same drivers, other shapes) with BCP_EXTENDED=1.
 # At the reduced shapes the dispatch may differ from the in-step one: a conv3_fwd_raw row falls back to conv3_fwd where the shape is
 # not served raw, and where a conv leaves no fused statistics (rows == 0) the fwd_stats / dgrad_bwdstats rows and the norm rows' "partial"
 # epilogue run without them.  These rows check the drivers and references on the simulator; the route itself is asserted on the device
 # (tests/test_gpu_product_ops.py: each row must launch its key, and the drivers require the fused routes there).
-@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] in ("la", "la_pre", "la_val") else pytest.mark.extended) for r in _reduced_rows()],
+@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] in ("la", "la_pre", "la_val", "lares", "lares_pre", "lares_val") else pytest.mark.extended) for r in _reduced_rows()],
                          ids=[P.row_id(r[0], r[1]) for r in _reduced_rows()])
 def test_product_op_reduced_on_simulator(emu_ops, wl, key, rkey):  # noqa: F811
     g = torch.Generator().manual_seed(5)
@@ -150,16 +150,20 @@ def test_every_step_op_has_a_driver():
     """a new op in a step, a pre-training step or a validation pass cannot go undriven: every op of STEP_KEYS has a driver, every table
     row is driven under its own workload or is the repeat of a row driven under an earlier one (same key, same flags), and the only
     rows outside the table are the keys a statistics-only norm call uses"""
-    assert sorted(P.STEP_KEYS) == sorted(["la", "pancreas", "acdc", "la_pre", "pancreas_pre", "acdc_pre", "la_val", "pancreas_val", "acdc_val", "la8"])
+    assert sorted(P.STEP_KEYS) == sorted(["la", "pancreas", "acdc", "la_pre", "pancreas_pre", "acdc_pre", "la_val", "pancreas_val", "acdc_val", "la8",
+                                          "lares", "lares_pre", "lares_val"])
     assert {k[0] for _, k in P.table_rows()} - set(UNDRIVEN) <= set(P.DRIVERS)
     rows = P.driven_rows()
-    assert len(P.table_rows()) == 671 and len(set(rows)) == len(rows)
+    assert len(P.table_rows()) == 671 + 221 and len(set(rows)) == len(rows)          # (221: the three residual workloads)
+    assert len([1 for wl, _ in P.table_rows() if not wl.startswith("lares")]) == 671
     first = [(wl, k) for wl, k in P.table_rows() if wl in ("la", "pancreas", "acdc")]
     assert len(first) == 223 and set(first) <= set(rows)                      # (the self-training table is driven as before)
     driven = {P._row_ident(wl, k) for wl, k in rows}
     assert all(P._row_ident(wl, k) in driven for wl, k in P.table_rows() if k[0] not in UNDRIVEN)
     extra = [k for _, k in rows if (_, k) not in set(P.table_rows())]
     assert all(k[0] == "norm_fwd" for k in extra), extra
+    for op in ("norm_fwd_res", "norm_bwd_res", "norm_eval_res", "axpy", "conv3_c1_fwd_stats", "conv3_c1_wgrad", "pw16_bwd"):      # the residual V-Net's
+        assert any(k[0] == op and wl.startswith("lares") for wl, k in rows), op
     for op in ("norm_eval", "sw_accumulate", "sw_finish", "overlap_counts", "plabel_argmax4", "mixloss_fwd", "mixloss_bwd", "conv3_c1_fwd", "pw16_fwd",
                "copy_channels"):
         assert any(k[0] == op for _, k in rows), op
@@ -412,3 +416,43 @@ def test_driver_rejects_corruption(emu_ops, case):  # noqa: F811
         closes = False
     print(f"[sensitivity] {case}: close() {'accepts' if closes else 'rejects'} it, rel-L2 {P.rel_l2(corrupt, clean):.2e} "
           f"({'accepted' if P.rel_l2(corrupt, clean) < 1e-4 else 'rejected'} at 1e-4)")
+
+
+# -------------------------------------------------------------------------------------------------- can the residual drivers fail?
+# (near-miss, the op of the residual row driven, its workload, the channel count of the row): the 16-channel rows carry every flag set --
+# block_nine's channel scale, block_one's broadcast residual from conv3_c1_fwd_stats rows, two norm groups
+RES_NEAR_MISSES = [("pattern_from_z", "norm_bwd_res", "lares"), ("residual_behind_activation", "norm_fwd_res", "lares"),
+                   ("neighbour_chan_scale", "norm_fwd_res", "lares"), ("neighbour_chan_scale", "norm_bwd_res", "lares"),
+                   ("bcast_row_off", "norm_fwd_res", "lares"), ("bcast_row_off", "norm_bwd_res", "lares"), ("bcast_row_off", "norm_eval_res", "lares_val"),
+                   ("group_statistics_swapped", "norm_fwd_res", "lares"), ("dres_without_chan_scale", "norm_bwd_res", "lares"),
+                   ("c1c2_from_z", "norm_bwd_res", "lares"), ("eval_batch_statistics", "norm_eval_res", "lares_val")]
+
+
+def test_near_misses_cover_the_list():
+    assert {n for n, _, _ in RES_NEAR_MISSES} == set(P.NEAR_MISSES)
+
+
+@pytest.mark.parametrize("miss,op,wl", RES_NEAR_MISSES, ids=[f"{m}-{o}" for m, o, _ in RES_NEAR_MISSES])
+def test_residual_driver_rejects_near_miss_reference(emu_ops, miss, op, wl):  # noqa: F811
+    """each residual driver on the simulator at the reduced 16-channel shape of its workload: with the right fp64 reference every row
+    passes; with a reference that is wrong the way a plausible kernel would be -- the ReLU pattern taken from z alone, relu(z) + r, the
+    neighbouring sample's channel scale, the broadcast residual one row off, group 0 normalised with group 1's statistics, dres without the
+    channel scale, the backward's two means from the z-only pattern, eval with batch statistics -- the same bound on the same inputs must
+    reject the (correct) kernel output"""
+    rows = [(w, k) for w, k in P.table_rows() if w == wl and k[0] == op and k[1][0][-1] == 16 and k[1][0][0] == 2 - (wl == "lares_val")]
+    assert rows, (op, wl)
+    n = 0
+    for w, key in rows:                       # (norm_bwd_res has two 16-channel rows: the full and the broadcast residual)
+        rkey = P.reduce_key(key)
+        P.run_row(emu_ops, torch.device("cpu"), w, rkey, torch.Generator().manual_seed(5), table_key=key)
+        P.NEAR_MISS, P.NEAR_MISS_HITS = miss, 0
+        try:
+            try:
+                P.run_row(emu_ops, torch.device("cpu"), w, rkey, torch.Generator().manual_seed(5), table_key=key)
+                assert P.NEAR_MISS_HITS == 0, f"{miss}: the near-miss reference was accepted at {rkey}"
+            except AssertionError as e:
+                assert P.NEAR_MISS_HITS > 0 and "accepted" not in str(e), e
+                n += 1
+        finally:
+            P.NEAR_MISS = None
+    assert n >= 1, f"{miss}: no {op} row applies it"
