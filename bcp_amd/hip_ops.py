@@ -719,12 +719,18 @@ class Ops:
         self._note_pack_section(wp)
         return self._no_amax(out)
 
+    def conv3_stat_rows(self, xshape, Cout, KD, groups):
+        """partial rows per normalisation group conv3_fwd_stats leaves for this shape; 0: not fused (it runs the plain conv3_fwd)"""
+        N, D, H, W, Cin = xshape
+        nbytes = self._ws_bytes("bcp_conv3_fwd_workspace_bytes", N, D, H, W, Cin, Cout, KD)
+        return self._ws_bytes("bcp_conv3_stat_rows", N, D, H, W, Cin, Cout, KD, int(groups), 1 if nbytes else 0)
+
     def conv3_fwd_stats(self, x, wp, bias, Cout, KD, groups):
         """conv + fused norm statistics -> (y, partial, rows); rows == 0: statistics not fused for this shape (partial None)"""
         self._chk(x, wp, bias)
         N, D, H, W, Cin = x.shape
         nbytes = self._ws_bytes("bcp_conv3_fwd_workspace_bytes", N, D, H, W, Cin, Cout, KD)
-        rows = self._ws_bytes("bcp_conv3_stat_rows", N, D, H, W, Cin, Cout, KD, groups, 1 if nbytes else 0)
+        rows = self.conv3_stat_rows(x.shape, Cout, KD, groups)
         if rows == 0:
             return self.conv3_fwd(x, wp, bias, Cout, KD), None, 0
         ws = self.workspace("conv3", nbytes, x) if nbytes else None
@@ -735,12 +741,17 @@ class Ops:
         self._note_pack_section(wp)
         return out, part, rows
 
+    def conv3_bwdstat_rows(self, dyshape, Cin, KD, groups):
+        """partial rows per group conv3_dgrad_bwdstats leaves for this shape; 0: not fused (it runs the plain dgrad)"""
+        N, D, H, W, Cout = dyshape
+        return self._ws_bytes("bcp_conv3_bwdstat_rows", N, D, H, W, Cout, int(Cin), KD, int(groups))
+
     def conv3_dgrad_bwdstats(self, dy, wd, Cin, KD, y_prev, stats_prev, act, groups):
         """dgrad whose epilogue also accumulates the backward statistics of the norm layer that consumes it (pre-norm tensor y_prev,
         statistics stats_prev): -> (da, partial, rows) for norm_bwd(partial=, nb=); rows == 0: not fused for this shape (plain dgrad)"""
         self._chk(dy, wd, y_prev, stats_prev)
         N, D, H, W, Cout = dy.shape
-        rows = self._ws_bytes("bcp_conv3_bwdstat_rows", N, D, H, W, Cout, Cin, KD, groups)
+        rows = self.conv3_bwdstat_rows(dy.shape, Cin, KD, groups)
         if rows == 0:
             return self.conv3_fwd(dy, wd, None, Cin, KD), None, 0
         nbytes = self._ws_bytes("bcp_conv3_fwd_workspace_bytes", N, D, H, W, Cout, Cin, KD)
@@ -772,12 +783,17 @@ class Ops:
         self.b.call("bcp_conv3_c1_fwd", _p(x), _p(w), _p(bias), _p(out), N, D, H, W, KD, self.stream(x))
         return out
 
+    def conv3_c1_stat_rows(self, xshape, KD, groups):
+        """partial rows per group conv3_c1_fwd_stats leaves for this shape; 0: not fused (it runs the plain conv3_c1_fwd)"""
+        N, D, H, W, _ = xshape
+        return self._ws_bytes("bcp_conv3_c1_stat_rows", N, D, H, W, KD, int(groups))
+
     def conv3_c1_fwd_stats(self, x, w, bias, KD, groups):
         """first layer + fused norm statistics -> (y, partial, rows), as conv3_fwd_stats"""
         self._chk(x, w, bias)
         N, D, H, W, Cin = x.shape
         assert Cin == 1 and w.shape[0] == 16
-        rows = self._ws_bytes("bcp_conv3_c1_stat_rows", N, D, H, W, KD, groups)
+        rows = self.conv3_c1_stat_rows(x.shape, KD, groups)
         if rows == 0:
             return self.conv3_c1_fwd(x, w, bias, KD), None, 0
         out = torch.empty((N, D, H, W, 16), dtype=torch.float32, device=x.device)

@@ -7,14 +7,21 @@ ReLU (bcp_norm_fwd_res / _bwd_res / _eval_res); same parameters and keys as the 
 Same constructor arguments, same `state_dict()` keys / shapes (259 / 60; groupnorm 172 / 118), same `parameters()` order,
 same call result: `(out_seg, features)` for the LA net, `[out]` for the pancreas net.  What differs is
 what runs: every layer is a call into libbcp_hip.so (NDHWC fp32, MFMA implicit-GEMM convs, fused
-norm+act(+dropout,+skip) streams), scheduled by `_forward_impl` / `_backward_impl` below; autograd
-sees ONE node per call (networks/_hipnet.py:NetFn).
+norm+act(+dropout,+skip) streams); autograd sees ONE node per call (networks/_hipnet.py:NetFn).
+
+The schedule is planned, then executed.  `plan_forward` / `plan_backward` decide every layer's route -- which Ops method produces the
+pre-norm tensor, which normalises, what the dgrad behind it leaves -- from shapes, mode and switches alone (host-side shape queries of the
+library: no tensor, no launch), and every exclusion rule between a fusion and a mode stands there, once.  `_forward_impl` /
+`_backward_impl` walk those records and call the named op; what the forward hands to the backward is a `_Saved` (named fields, the routes
+included).  Tests read the same records (tests/residual_checks.py, gnorm_seam_checks.py, test_plan_product.py).
 
 Topology (networks/VNet.py:167-186, 213-239): block_one(1->16) dw block_two(2x32) dw block_three(3x64) dw
 block_four(3x128) dw block_five(3x256) [Dropout3d] up+x4 block_six(3x128) up+x3 block_seven(3x64) up+x2
 block_eight(2x32) up+x1 block_nine(16) [Dropout3d] out_conv(16->n_classes, 1x1x1).
 """
 from __future__ import annotations
+
+import math
 
 import torch
 import torch.nn as nn
@@ -37,6 +44,70 @@ class _Layer:
         self.drop = None         # 'x5' / 'x9': Dropout3d on this layer's output
         self.closing = False     # has_residual: last 3x3x3 layer of a block -- the block's input is added in front of its ReLU
         self.block_first = False  # has_residual: first 3x3x3 layer of a block -- its input is the block input the closing layer adds
+
+
+class _Route:
+    """one layer's forward route (VNet.plan_forward).  producer / norm: the names of the Ops methods the forward calls -- one name twice where
+    one op is both (the recomputing fusions).  nslabs: split-K slabs the producer leaves raw (1: a plain tensor); rows: statistics rows per
+    group its epilogue leaves (0: none -- conv3_fwd_stats / conv3_c1_fwd_stats then run their plain conv themselves); stats_only: the norm writes its table only, the fused head applies it; dropout: a Dropout3d
+    channel scale rides in the norm's epilogue; xshape / yshape: the producer's input and output"""
+    __slots__ = ("producer", "norm", "stats_only", "nslabs", "rows", "dropout", "closing", "xshape", "yshape")
+
+    @property
+    def keeps_y(self):
+        """the layer writes its pre-norm tensor (a recomputing fusion does not)"""
+        return self.producer != self.norm
+
+    @property
+    def bwdstats_ok(self):
+        """the dgrad behind this layer may leave its norm's backward statistics in its epilogue: there is a pre-norm tensor to read, no
+        dropout epilogue, and the ReLU pattern follows from z alone (not behind the closing layer of a residual block)"""
+        return self.keeps_y and not self.dropout and not self.closing
+
+
+class _BwdRoute:
+    """one layer's backward route (VNet.plan_backward).  norm: the op that does the norm's backward (the head's, where that goes through);
+    partial: it takes the backward-statistics rows the dgrad behind it left; dgrad: the layer's own dgrad op (None: the first layer), which
+    writes nslabs raw split-K slabs (1: a plain tensor) and leaves `rows` statistics rows per group for the layer in front (0: none -- conv3_dgrad_bwdstats then runs the plain dgrad itself)"""
+    __slots__ = ("norm", "partial", "dgrad", "nslabs", "rows")
+
+
+class _Plan:
+    """one pass's routes: G normalisation groups, the head's op, a _Route per layer, running-statistics updates to count"""
+    __slots__ = ("G", "head", "layers", "bn_ticks")
+
+    def __init__(self, G, head, layers, bn_ticks):
+        self.G, self.head, self.layers, self.bn_ticks = G, head, layers, bn_ticks
+
+
+class _SavedLayer:
+    """what a layer's backward reads: input, pre-norm tensor (None: recomputed), statistics, Dropout3d channel scale, the block input a
+    closing layer added (has_residual) and the layer's route"""
+    __slots__ = ("x", "y", "stats", "cs", "r_in", "route")
+
+    def __init__(self, x, y, stats, cs, r_in, route):
+        self.x, self.y, self.stats, self.cs, self.r_in, self.route = x, y, stats, cs, r_in, route
+
+
+class _Saved:
+    """what a saving forward hands to its backward -- one object per pass (launch plans key the backward on its identity)"""
+    __slots__ = ("plan", "layers", "head_in")
+
+    def __init__(self, plan):
+        self.plan, self.layers, self.head_in = plan, [], None     # head_in: the head's input, None when the head is fused
+
+    G = property(lambda self: self.plan.G)
+
+    def __getitem__(self, i):
+        """read-only view in the tuple layout this structure replaced -- (x, y, stats, cs, G[, r_in]) per layer, then (head_in,) -- for
+        callers written against it; nothing in the package or its tests reads it"""
+        rows = [(s.x, s.y, s.stats, s.cs, self.G) + ((s.r_in,) if s.route.closing else ()) for s in self.layers]
+        return (rows + [(self.head_in,)])[i]
+
+
+def _norm_params(bn):
+    """(gamma, beta, running mean, running variance) of a BatchNorm layer; InstanceNorm has no module: four Nones"""
+    return (None,) * 4 if bn is None else (bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
 
 
 class VNet(HipNet):
@@ -194,10 +265,130 @@ class VNet(HipNet):
             return logits, (None if f is None else f.permute(0, 4, 1, 2, 3))
         return [logits]
 
-    # ------------------------------------------------------------------ schedule
+    # ------------------------------------------------------------------ schedule: the planner (no tensor, no launch)
+    def plan_forward(self, N, D, H, W, groups, save, training, dropout, keep_saved=False):
+        """every layer's forward route for an input of extents (N, D, H, W) -> _Plan.  Decided from the layer list, the shapes, the mode
+        (`training`; `dropout`: the Dropout3d sites draw; `keep_saved`: a test wants every pre-norm tensor) and the class switches alone --
+        it asks the library's host-side shape queries and nothing else, so it runs without a GPU.  Every exclusion rule stands here, once."""
+        ops, gn, bnorm = self.ops, self._gn, self.norm == "batchnorm"
+        G = groups if bnorm else N
+        # GroupNorm evaluates exactly as it trains: every choice that asks "training?" for the sake of batch statistics takes the training
+        # answer in both modes, so model.eval() gives the train-mode bits (dropout apart)
+        batch_stats = training or gn
+        last = len(self._layers) - 1
+        Ll = self._layers[last]
+        # the head normalises on its way in (bcp_pw16_fwd_norm): block_nine's 16-channel activation is never written (statistics only there)
+        fuse_head = self.fuse_head and batch_stats and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32 and not Ll.closing
+        routes, sp = [], (D, H, W)
+        for li, L in enumerate(self._layers):
+            r = _Route()
+            r.xshape = (N,) + sp + (L.cin,)
+            sp = tuple(e // 2 for e in sp) if L.kind == "dw" else tuple(2 * e for e in sp) if L.kind == "up" else sp
+            r.yshape = (N,) + sp + (L.cout,)
+            r.closing, r.dropout, r.stats_only, r.nslabs, r.rows = L.closing, dropout and L.drop is not None, li == last and fuse_head, 1, 0
+            # a fusion whose norm reads something else than a plain pre-norm tensor: training-mode BatchNorm / InstanceNorm only, and never
+            # where another op reads that tensor -- the closing layer of a residual block (bcp_norm_fwd_res / _eval_res apply relu(z + r)
+            # themselves) and the layer in front of the fused head
+            fusable = training and not gn and not L.closing and not r.stats_only
+            # ... and one that never writes the pre-norm tensor (recompute): not at a Dropout3d site, not when a test wants that tensor
+            recompute = fusable and L.drop is None and not keep_saved
+            if L.kind == "c1":
+                if recompute and self.fuse_c1 and not L.skip_pop and ops.conv3_c1_norm_ok(r.xshape, 3, G):
+                    r.producer = "conv3_c1_norm_fwd"      # conv + norm + ReLU with recompute: the 16-channel pre-norm tensor is never written
+                elif batch_stats:                         # statistics in the epilogue: no pass over the 16-channel y
+                    r.producer, r.rows = "conv3_c1_fwd_stats", ops.conv3_c1_stat_rows(r.xshape, 3, G)
+                else:
+                    r.producer = "conv3_c1_fwd"
+            elif L.kind == "c3":
+                # deep levels (<= 4096 rows per normalisation group) whose conv runs split-K: the conv leaves its raw slabs and the norm's
+                # statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs) -- no slab-sum launch
+                if fusable and ops.norm_slabs_ok(G, N * sp[0] * sp[1] * sp[2] // G, L.cout):
+                    r.nslabs = max(ops.conv3_nslabs(r.xshape, L.cout, 3), 1)
+                if r.nslabs > 1:
+                    r.producer = "conv3_fwd_raw"
+                elif batch_stats or L.bn is None:
+                    r.producer, r.rows = "conv3_fwd_stats", ops.conv3_stat_rows(r.xshape, L.cout, 3, G)
+                else:                                     # eval-mode BatchNorm needs no batch statistics
+                    r.producer = "conv3_fwd"
+            elif L.kind == "up" and recompute and (not save or self.UP_RECOMPUTE_GRAD) and ops.up_norm_rows(r.xshape, L.cout, G) > 0:
+                # (round 6) transposed conv + norm + ReLU + skip add with recompute (bcp_up_fwd_norm): the pre-norm tensor is never written
+                r.producer = "up_fwd_norm"
+            else:
+                # (round 6) the norm's statistics from the GEMM's epilogue where the shape has them (library option k2_stats = 0: never)
+                r.rows = ops.k2_stat_rows(int(L.kind == "up"), r.xshape, L.cout, G) if batch_stats else 0
+                r.producer = "k2_fwd_stats" if r.rows else "down_fwd" if L.kind == "dw" else "up_fwd"
+            if L.closing:
+                r.norm = "norm_fwd_res" if training else "norm_eval_res"
+            elif r.producer in ("conv3_c1_norm_fwd", "up_fwd_norm"):
+                r.norm = r.producer
+            elif r.producer == "conv3_fwd_raw":
+                r.norm = "norm_fwd_slabs"
+            elif gn:        # statistics (the producer's rows, or a pass of its own) -> finalize -> apply; in front of the fused head the table only
+                r.norm = "gnorm_fwd"
+            else:           # model.eval(): running statistics, no update (validation / sliding-window inference, SURVEY 8f-1)
+                r.norm = "norm_eval" if L.bn is not None and not training else "norm_fwd"
+            routes.append(r)
+        return _Plan(G, "pw16_fwd_norm" if fuse_head else "pw16_fwd", routes, G if bnorm and training else 0)
+
+    def plan_call(self, N, D, H, W, save):
+        """plan_forward in the mode this network is in: what its next (or last) call with such an input and these `forward` arguments takes"""
+        return self.plan_forward(N, D, H, W, getattr(self, "_groups", 1), save, self.training,
+                                 self.has_dropout and self.training and not getattr(self, "_turnoff_drop", False), getattr(self, "_keep_saved", False))
+
+    def plan_backward(self, plan):
+        """the backward routes behind a saving forward's plan -> (the head's backward op, [_BwdRoute per layer]); launch-free like plan_forward"""
+        ops, gn, G, R = self.ops, self._gn, plan.G, plan.layers
+        last = len(self._layers) - 1
+        if plan.head != "pw16_fwd_norm":
+            head = "pw16_bwd"
+        else:       # the fused head goes THROUGH the last layer's norm (the one-call form makes BatchNorm's backward coefficients itself)
+            head = "pw16_bwd_norm_bwd" if ops.HEAD_BWD_FUSED and not self._layers[last].skip_pop and not gn else "pw16_bwd_norm"
+        out = [None] * (last + 1)
+        nsl, partial = 1, False          # what the dgrad behind the layer leaves: raw split-K slabs (> 1), the layer's backward-statistics rows
+        for li in range(last, -1, -1):
+            L, r, b = self._layers[li], R[li], _BwdRoute()
+            if r.closing:
+                b.norm = "norm_bwd_res"
+            elif li == last and head == "pw16_bwd_norm_bwd":
+                b.norm = head
+            elif r.norm == "up_fwd_norm":        # (round 6) y = up(x_in) again, inside both passes of the norm's backward
+                b.norm = "up_norm_bwd"
+            elif r.norm == "conv3_c1_norm_fwd":  # ... and with C1_BWD_FUSED the layer's weight gradient in the same pass: no dy
+                b.norm = "conv3_c1_norm_bwd_wgrad" if ops.C1_BWD_FUSED else "conv3_c1_norm_bwd"
+            elif r.norm == "gnorm_fwd":
+                b.norm = "gnorm_bwd"
+            else:                                # deep levels: the backward-statistics pass sums the dgrad's raw slabs (bcp_norm_bwd_slabs)
+                b.norm = "norm_bwd_slabs" if nsl > 1 else "norm_bwd"
+            assert b.norm in ("norm_bwd", "gnorm_bwd", "norm_bwd_slabs") or (nsl == 1 and not partial), (L.name, b.norm, nsl, partial)
+            b.partial, nsl, partial = partial, 1, False
+            # the consumer of this layer's dgrad is the norm backward of the layer in front.  has_residual: the dgrad of a block's FIRST layer
+            # is joined with the shortcut's gradient first -- a plain tensor, and no statistics taken from it in front of the join
+            prev = R[li - 1] if li > 0 and not L.block_first else None
+            b.nslabs, b.rows = 1, 0
+            if L.kind == "c1":
+                b.dgrad = None
+            elif L.kind == "c3":
+                # deep levels: the raw split-K slabs (no slab-sum launch); else, without a dropout epilogue in front, the dgrad epilogue
+                # leaves the backward statistics (bcp_conv3_dgrad_bwdstats) where the shape is served
+                if prev is not None and prev.keeps_y and not gn and ops.norm_slabs_ok(G, math.prod(r.xshape) // (L.cin * G), L.cin):
+                    b.nslabs = max(ops.conv3_nslabs(r.yshape, L.cin, 3), 1)
+                if b.nslabs > 1:
+                    b.dgrad = "conv3_fwd_raw"
+                elif prev is not None and prev.bwdstats_ok:
+                    b.dgrad, b.rows = "conv3_dgrad_bwdstats", ops.conv3_bwdstat_rows(r.yshape, L.cin, 3, G)
+                else:
+                    b.dgrad = "conv3_fwd"
+            else:
+                # (round 6) bcp_down_dgrad_bwdstats / bcp_up_dgrad_bwdstats where the shape is served: no k_col_partial<1> pass over (y, da)
+                if prev is not None and prev.bwdstats_ok:
+                    b.rows = ops.k2_bwdstat_rows(int(L.kind == "up"), r.yshape, L.cin, G)
+                b.dgrad = "k2_dgrad_bwdstats" if b.rows else "down_dgrad" if L.kind == "dw" else "up_dgrad"
+            nsl, partial = b.nslabs, b.rows > 0
+            out[li] = b
+        return head, out
+
+    # ------------------------------------------------------------------ schedule: the executors (dispatch on the records)
     def _chan_scale(self, L, N, dev):
-        if L.drop is None or not self.has_dropout or not self.training or getattr(self, "_turnoff_drop", False):
-            return None
         if self.drop_masks is not None:
             m = self.drop_masks[L.drop]
             return (m.to(device=dev, dtype=torch.float32) * 2.0).contiguous()
@@ -207,123 +398,75 @@ class VNet(HipNet):
     def _forward_impl(self, xcl, save):
         ops = self.ops
         N = xcl.shape[0]
-        G = getattr(self, "_groups", 1) if self.norm == "batchnorm" else N
+        plan = self.plan_call(N, xcl.shape[1], xcl.shape[2], xcl.shape[3], save)
+        G = plan.G
         h = xcl
         skips = []
-        saved = []
+        saved = _Saved(plan) if save else None
         feat = None
-        last = len(self._layers) - 1
-        Ll = self._layers[last]
-        gn = self._gn
-        # GroupNorm evaluates exactly as it trains: every kernel choice below that asks "training?" for the sake of batch statistics takes the
-        # training answer in both modes, so model.eval() gives the train-mode bits (dropout apart)
-        tr = self.training or gn
-        fuse_head = (self.fuse_head and tr and Ll.kind == "c3" and Ll.cout == 16 and not Ll.skip_pop and N <= 32 and not Ll.closing)
         r_in = None                      # has_residual: the input of the block being walked
-        for li, L in enumerate(self._layers):
+        for li, (L, r) in enumerate(zip(self._layers, plan.layers)):
             w, b = L.conv.weight, L.conv.bias
-            part, nb = None, 0
+            y, part, nb = None, None, 0
             if L.skip_push:
                 skips.append(h)
             if L.block_first:
                 r_in = h
-            # deep levels (<= 4096 rows per normalisation group) whose conv runs split-K: the conv leaves its raw slabs and the norm's
-            # statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs) -- no slab-sum launch; decided per layer below
-            sp = h.shape[1] * h.shape[2] * h.shape[3]
-            # (a closing layer of a residual block takes no fusion that applies relu(z) itself: bcp_norm_fwd_res / _eval_res read a plain y)
-            slabs_ok = (self.training and not gn and L.kind == "c3" and not L.closing and not (li == last and fuse_head)
-                        and ops.norm_slabs_ok(G, N * sp // G, L.cout))
-            small = False
-            src, nsl, bsrc = None, 1, None
-            fused_c1 = False
-            fused_up = False
-            if L.kind == "c1":
-                fused_c1 = (self.fuse_c1 and self.training and not gn and not small and not L.skip_pop and L.drop is None and not L.closing and not getattr(self, "_keep_saved", False)
-                            and not (li == last and fuse_head) and ops.conv3_c1_norm_ok(h.shape, 3, G))
-                if fused_c1:
-                    y = None       # conv + norm + ReLU with recompute (bcp_conv3_c1_norm_fwd): the 16-channel pre-norm tensor is never written
-                elif tr and not small:
-                    y, part, nb = ops.conv3_c1_fwd_stats(h, w.data, b.data, 3, G)      # statistics in the epilogue: no pass over the 16-channel y
-                else:
-                    y = ops.conv3_c1_fwd(h, w.data, b.data, 3)
-            elif L.kind == "c3":
+            p = r.producer           # (the recomputing producers, conv3_c1_norm_fwd and up_fwd_norm, ARE the norm op below: nothing here)
+            if L.kind == "c3":
                 wf, _ = self.conv3_packed(("c3", li), save)
-                sk = ops.conv3_nslabs(h.shape, L.cout, 3) if slabs_ok else 0
-                if sk > 1:
-                    src, nsl, bsrc, small = ops.conv3_fwd_raw(h, wf, L.cout, 3, sk), sk, b.data, True
-                elif tr or L.bn is None:
-                    y, part, nb = ops.conv3_fwd_stats(h, wf, b.data, L.cout, 3, G)
-                else:
-                    y = ops.conv3_fwd(h, wf, b.data, L.cout, 3)          # eval-mode BatchNorm needs no batch statistics
-            elif (L.kind == "up" and self.training and not gn and L.drop is None and not (li == last and fuse_head) and not getattr(self, "_keep_saved", False)
-                  and (not save or self.UP_RECOMPUTE_GRAD) and ops.up_norm_rows(h.shape, L.cout, G) > 0):
-                # (round 6) transposed conv + norm + ReLU + skip add with recompute (bcp_up_fwd_norm): the pre-norm tensor is never written
+            elif L.kind != "c1":
                 bp, _ = self.k2_packed(("k2", li), save)
-                fused_up, y = True, None
-            else:
-                kind = 0 if L.kind == "dw" else 1
-                bp, _ = self.k2_packed(("k2", li), save)
-                # (round 6) the norm's statistics from the GEMM's epilogue where the shape has them: no statistics pass over y
-                if tr and ops.k2_stat_rows(kind, h.shape, L.cout, G) > 0:       # (library option k2_stats = 0: never)
-                    y, part, nb = ops.k2_fwd_stats(kind, h, bp, b.data, L.cout, G)
-                elif kind == 0:
-                    y = ops.down_fwd(h, bp, b.data, L.cout)
-                else:
-                    y = ops.up_fwd(h, bp, b.data, L.cout)
+            if p == "conv3_c1_fwd_stats":
+                y, part, nb = ops.conv3_c1_fwd_stats(h, w.data, b.data, 3, G)
+            elif p == "conv3_c1_fwd":
+                y = ops.conv3_c1_fwd(h, w.data, b.data, 3)
+            elif p == "conv3_fwd_raw":
+                src = ops.conv3_fwd_raw(h, wf, L.cout, 3, r.nslabs)
+            elif p == "conv3_fwd_stats":
+                y, part, nb = ops.conv3_fwd_stats(h, wf, b.data, L.cout, 3, G)
+            elif p == "conv3_fwd":
+                y = ops.conv3_fwd(h, wf, b.data, L.cout, 3)
+            elif p == "k2_fwd_stats":
+                y, part, nb = ops.k2_fwd_stats(int(L.kind == "up"), h, bp, b.data, L.cout, G)
+            elif p == "down_fwd":
+                y = ops.down_fwd(h, bp, b.data, L.cout)
+            elif p == "up_fwd":
+                y = ops.up_fwd(h, bp, b.data, L.cout)
             res = skips.pop() if L.skip_pop else None
-            cs = self._chan_scale(L, N, xcl.device)
-            if L.closing:
-                bn = L.bn
-                if self.training:
-                    a, stats = ops.norm_fwd_res(y, G, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, H.ACT_RELU, r_in, chan_scale=cs,
-                                                partial=part, nb=nb)
-                else:
-                    a, stats = ops.norm_eval_res(y, bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var, H.ACT_RELU, r_in), None
-            elif fused_up:
-                bn = L.bn
-                a, stats = ops.up_fwd_norm(h, bp, b.data, L.cout, G, *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
-                                                                      if bn is not None else (None,) * 4), H.ACT_RELU, residual=res)
-            elif fused_c1:
-                bn = L.bn
-                a, stats = ops.conv3_c1_norm_fwd(h, w.data, b.data, 3, G, *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
-                                                                              if bn is not None else (None,) * 4), H.ACT_RELU)
-            elif small:
-                bn = L.bn
-                a, stats, y = ops.norm_fwd_slabs(src, nsl, bsrc, G,
-                                                 *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4),
-                                                 H.ACT_RELU, chan_scale=cs, residual=res)
-            elif gn:
-                # GroupNorm: statistics (the producer's rows, or a pass of its own) -> finalize -> apply; in front of the fused head the table only
-                head = li == last and fuse_head
-                a, stats = ops.gnorm_fwd(y, L.bn.weight.data, L.bn.bias.data, H.ACT_RELU, chan_scale=cs, residual=None if head else res,
-                                         partial=part, nb=nb, stats_only=head)
-            elif li == last and fuse_head:
-                # the head normalises on its way in: block_nine's 16-channel activation is never written (statistics only here)
-                bn = L.bn
-                a, stats = ops.norm_fwd(y, G, *((bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var) if bn is not None else (None,) * 4),
-                                        H.ACT_RELU, chan_scale=cs, partial=part, nb=nb, stats_only=True)
-            elif L.bn is not None and not self.training:
-                # model.eval(): running statistics, no update (validation / sliding-window inference)
-                a, stats = ops.norm_eval(y, L.bn.weight.data, L.bn.bias.data, L.bn.running_mean, L.bn.running_var, H.ACT_RELU, residual=res), None
-            elif L.bn is not None:
-                a, stats = ops.norm_fwd(y, G, L.bn.weight.data, L.bn.bias.data, L.bn.running_mean, L.bn.running_var, H.ACT_RELU,
-                                        chan_scale=cs, residual=res, partial=part, nb=nb)
+            cs = self._chan_scale(L, N, xcl.device) if r.dropout else None
+            n, stats = r.norm, None
+            if n == "norm_fwd_res":
+                a, stats = ops.norm_fwd_res(y, G, *_norm_params(L.bn), H.ACT_RELU, r_in, chan_scale=cs, partial=part, nb=nb)
+            elif n == "norm_eval_res":
+                a = ops.norm_eval_res(y, *_norm_params(L.bn), H.ACT_RELU, r_in)
+            elif n == "up_fwd_norm":
+                a, stats = ops.up_fwd_norm(h, bp, b.data, L.cout, G, *_norm_params(L.bn), H.ACT_RELU, residual=res)
+            elif n == "conv3_c1_norm_fwd":
+                a, stats = ops.conv3_c1_norm_fwd(h, w.data, b.data, 3, G, *_norm_params(L.bn), H.ACT_RELU)
+            elif n == "norm_fwd_slabs":
+                a, stats, y = ops.norm_fwd_slabs(src, r.nslabs, b.data, G, *_norm_params(L.bn), H.ACT_RELU, chan_scale=cs, residual=res)
+            elif n == "gnorm_fwd":
+                a, stats = ops.gnorm_fwd(y, L.bn.weight.data, L.bn.bias.data, H.ACT_RELU, chan_scale=cs, residual=res, partial=part, nb=nb,
+                                         stats_only=r.stats_only)
+            elif n == "norm_eval":
+                a = ops.norm_eval(y, *_norm_params(L.bn), H.ACT_RELU, residual=res)
             else:
-                a, stats = ops.norm_fwd(y, G, None, None, None, None, H.ACT_RELU, chan_scale=cs, residual=res, partial=part, nb=nb)
+                a, stats = ops.norm_fwd(y, G, *_norm_params(L.bn), H.ACT_RELU, chan_scale=cs, residual=res, partial=part, nb=nb,
+                                        stats_only=r.stats_only)
             if save:
-                saved.append((h, y, stats, cs, G) + ((r_in,) if L.closing else ()))
+                saved.layers.append(_SavedLayer(h, y, stats, cs, r_in if r.closing else None, r))
             h = a
             if L.drop == "x5" and getattr(self, "_want_feat", False) and min(a.shape[1:4]) >= 3:
                 feat = ops.maxpool3d_k3s2_fwd(a)      # pool(features[4]): the reference's second return value (networks/VNet.py:286-290)
-        if self.norm == "batchnorm" and self.training:
-            for _ in range(G):
-                self._nbt_tick()
-        if fuse_head:
+        for _ in range(plan.bn_ticks):
+            self._nbt_tick()
+        if plan.head == "pw16_fwd_norm":
             logits = ops.pw16_fwd_norm(y, stats, cs, G, H.ACT_RELU, self._out.weight.data, self._out.bias.data, self.n_classes)
         else:
             logits = ops.pw16_fwd(h, self._out.weight.data, self._out.bias.data, self.n_classes)
         if save:
-            saved.append((h,))          # None when the head is fused: the backward recomputes it from saved[last]
+            saved.head_in = h           # None when the head is fused: the backward recomputes it from the last layer's record
         logits._bcp_feat = feat         # rides on the result object (launch plans keep it; _run_forward hands out a copy)
         return logits, saved
 
@@ -339,24 +482,22 @@ class VNet(HipNet):
 
     def _backward_impl(self, saved, dout):
         ops = self.ops
-        G = saved[0][4]
+        G = saved.G
         dlogits = dout if dout.is_contiguous() else dout.contiguous()
         self.begin_backward()
-        (h_last,) = saved[-1]
-        dy_head = None                   # the fused head went THROUGH the last layer's norm: that layer's dy, no norm_bwd of its own
-        if h_last is None:
-            Ll = self._layers[-1]
-            _, y9, st9, cs9, _ = saved[len(self._layers) - 1]
-            if ops.HEAD_BWD_FUSED and not Ll.skip_pop and not self._gn:      # (the one-call form makes BatchNorm's backward coefficients itself)
-                dg9, db9 = (Ll.bn.weight.grad, Ll.bn.bias.grad) if Ll.bn is not None else (None, None)
-                dy_head = ops.pw16_bwd_norm_bwd(y9, st9, cs9, G, H.ACT_RELU, dlogits, self._out.weight.data, self._out.weight.grad,
-                                                self._out.bias.grad, dg9, db9, norm_accumulate=Ll.bn is not None, accumulate=True)
-                dh = None
-            else:
-                dh = ops.pw16_bwd_norm(y9, st9, cs9, G, H.ACT_RELU, dlogits, self._out.weight.data, self._out.weight.grad, self._out.bias.grad,
-                                       accumulate=True)
+        head, routes = self.plan_backward(saved.plan)
+        s9, dy_head = saved.layers[-1], None
+        if head == "pw16_bwd_norm_bwd":      # that layer's dy comes out of the head's call: no norm backward of its own
+            bn9 = self._layers[-1].bn
+            dg9, db9 = (bn9.weight.grad, bn9.bias.grad) if bn9 is not None else (None, None)
+            dy_head = ops.pw16_bwd_norm_bwd(s9.y, s9.stats, s9.cs, G, H.ACT_RELU, dlogits, self._out.weight.data, self._out.weight.grad,
+                                            self._out.bias.grad, dg9, db9, norm_accumulate=bn9 is not None, accumulate=True)
+            dh = None
+        elif head == "pw16_bwd_norm":
+            dh = ops.pw16_bwd_norm(s9.y, s9.stats, s9.cs, G, H.ACT_RELU, dlogits, self._out.weight.data, self._out.weight.grad, self._out.bias.grad,
+                                   accumulate=True)
         else:
-            dh = ops.pw16_bwd(h_last, dlogits, self._out.weight.data, self._out.weight.grad, self._out.bias.grad, accumulate=True)
+            dh = ops.pw16_bwd(saved.head_in, dlogits, self._out.weight.data, self._out.weight.grad, self._out.bias.grad, accumulate=True)
         skip_grads = []
         pend = []
 
@@ -376,44 +517,40 @@ class VNet(HipNet):
             for j in pend:       # (data parallelism: the flat gradient buffer is final from this layer's first parameter on -- bucket hook)
                 self._grads_final_from(j[5], j[2])
             pend.clear()
-        nsl = 1                          # dh is a plain gradient tensor (1) or the raw split-K slabs of the dgrad that produced it (> 1)
         bpart, bnb = None, 0             # backward-statistics partials of THIS layer's norm, left by the dgrad that produced dh
         for li in range(len(self._layers) - 1, -1, -1):
-            L = self._layers[li]
-            x_in, y, stats, cs = saved[li][:4]
+            L, s, r = self._layers[li], saved.layers[li], routes[li]
+            x_in, y, stats, cs = s.x, s.y, s.stats, s.cs
             w = L.conv.weight
             da = dh
             dg, db = (L.bn.weight.grad, L.bn.bias.grad) if L.bn is not None else (None, None)
-            if L.closing:
+            n = r.norm
+            if n == "norm_bwd_res":
                 # g = da * chan_scale * [z + r > 0] feeds the norm backward and, as dres, the gradient of the block input (block_one's r is the
                 # network input: no dres)
-                assert nsl == 1 and bpart is None
-                dy, dres = ops.norm_bwd_res(y, da, saved[li][5], G, stats, H.ACT_RELU, dg, db, True, chan_scale=cs, want_dres=li > 0)
-            elif dy_head is not None:
-                dy, dy_head = dy_head, None
-            elif y is None and L.kind == "up":     # (round 6) the recomputing transposed conv: y = up(x_in) again, inside both passes of the norm's backward
-                assert nsl == 1 and cs is None
+                dy, dres = ops.norm_bwd_res(y, da, s.r_in, G, stats, H.ACT_RELU, dg, db, True, chan_scale=cs, want_dres=li > 0)
+            elif n == "pw16_bwd_norm_bwd":
+                dy = dy_head
+            elif n == "up_norm_bwd":
                 bpf, _ = self.k2_packed(("k2", li), True)      # (the FORWARD pack: y is recomputed)
                 dy = ops.up_norm_bwd(x_in, bpf, L.conv.bias.data, L.cout, G, stats, da, H.ACT_RELU, dg, db, L.bn is not None)
-            elif y is None:     # the fused first layer: its pre-norm tensor is recomputed from the input (bcp_conv3_c1_norm_bwd)
-                assert L.kind == "c1" and nsl == 1
-                if ops.C1_BWD_FUSED:      # ... and the layer's weight gradient in the same pass: no dy, no launch left behind the main stream's last one
-                    ops.conv3_c1_norm_bwd_wgrad(x_in, w.data, L.conv.bias.data, 3, G, stats, da, H.ACT_RELU, w.grad, dg, db, L.bn is not None,
-                                                dw_accumulate=True)
-                    flush_wgrads()
-                    self._grads_final_from(w, da)
-                    break
+            elif n == "conv3_c1_norm_bwd_wgrad":      # no dy, no launch left behind the main stream's last one
+                ops.conv3_c1_norm_bwd_wgrad(x_in, w.data, L.conv.bias.data, 3, G, stats, da, H.ACT_RELU, w.grad, dg, db, L.bn is not None,
+                                            dw_accumulate=True)
+                flush_wgrads()
+                self._grads_final_from(w, da)
+                break
+            elif n == "conv3_c1_norm_bwd":      # the fused first layer: its pre-norm tensor is recomputed from the input
                 dy = ops.conv3_c1_norm_bwd(x_in, w.data, L.conv.bias.data, 3, G, stats, da, H.ACT_RELU, dg, db, L.bn is not None)
-            elif self._gn:
+            elif n == "gnorm_bwd":
                 # conv biases in front of GroupNorm layers with more than one channel per group receive their gradient (DESIGN.md "bias gradients")
                 dy = ops.gnorm_bwd(y, da, stats, L.bn.weight.data, H.ACT_RELU, dg, db, L.conv.bias.grad if L.cout > 16 else None, True,
                                    chan_scale=cs, partial=bpart, nb=bnb)
-            elif nsl > 1:
-                # deep levels: dh is the raw split-K slabs of the dgrad that produced it; the backward-statistics pass sums them (bcp_norm_bwd_slabs)
-                dy, da = ops.norm_bwd_slabs(y, da, nsl, G, stats, H.ACT_RELU, dg, db, L.bn is not None, chan_scale=cs)
+            elif n == "norm_bwd_slabs":      # dh is the raw split-K slabs of the dgrad that produced it
+                dy, da = ops.norm_bwd_slabs(y, da, routes[li + 1].nslabs, G, stats, H.ACT_RELU, dg, db, L.bn is not None, chan_scale=cs)
             else:
                 dy = ops.norm_bwd(y, da, G, stats, H.ACT_RELU, dg, db, L.bn is not None, chan_scale=cs, partial=bpart, nb=bnb)
-            nsl, bpart, bnb = 1, None, 0
+            bpart, bnb = None, 0
             if L.skip_pop:
                 skip_grads.append(da)       # d(out)/d(skip) = identity: the skip source gets `da` itself
             gw, acc = w.grad, True
@@ -422,50 +559,39 @@ class VNet(HipNet):
             # The weight gradient of a layer has no consumer inside the backward pass: it runs on a side stream underneath
             # the dgrad -> norm_bwd critical path (the deep levels' kernels are too small to fill 256 CUs on their own).
             # (round 6) every fork onto the side stream is an event record between two kernels of the MAIN stream -- a 5-7 us gap in front of
-            # the dgrad that follows (kernel trace, gpurun_out/r06_s31) -- so the small layers' weight gradients go over in batches of
-            # WGRAD_DEFER layers behind ONE fork; the large layers (>= 2^22 elements of dy) fork at once, as before
+            # the dgrad that follows -- so the small layers' weight gradients go over in batches of WGRAD_DEFER layers behind ONE fork; the
+            # large layers (>= 2^22 elements of dy) fork at once, as before
             pend.append((L.kind, x_in, dy, gw, acc, w))
             if dy.numel() >= (1 << 22) or len(pend) >= self.WGRAD_DEFER:
                 flush_wgrads()
-            if L.kind == "c1":
+            d = r.dgrad
+            prev = saved.layers[li - 1] if li > 0 else None      # (a *_dgrad_bwdstats epilogue reads its pre-norm tensor and statistics)
+            if d is None:
                 dh = None
             elif L.kind == "c3":
                 _, wd = self.conv3_packed(("c3", li), True)
-                # the consumer of this dgrad is the previous layer's norm backward: at the deep levels it takes the raw split-K slabs
-                # (no slab-sum launch); the previous layer must have a pre-norm tensor of its own (not the recomputing first layer)
-                # (has_residual: the dgrad of a block's FIRST layer is joined with the shortcut's gradient below -- a plain tensor, and no
-                #  statistics of the layer in front taken from it before the join.  A 3x3x3 layer never faces a closing layer: that ends its block)
-                sk = (ops.conv3_nslabs(dy.shape, L.cin, 3) if li > 0 and saved[li - 1][1] is not None and not self._gn and not L.block_first
-                      and ops.norm_slabs_ok(G, x_in.numel() // (L.cin * G), L.cin) else 0)
-                if sk > 1:
-                    dh, nsl = ops.conv3_fwd_raw(dy, wd, L.cin, 3, sk), sk
-                elif li > 0 and saved[li - 1][3] is None and saved[li - 1][1] is not None and not L.block_first:      # (a recomputing layer in front keeps no pre-norm tensor)
-                    # conv -> conv edge without a dropout epilogue: the dgrad epilogue leaves the previous norm layer's backward statistics
-                    # (bcp_conv3_dgrad_bwdstats; a plain dgrad when the shape is not served)
-                    dh, bpart, bnb = ops.conv3_dgrad_bwdstats(dy, wd, L.cin, 3, saved[li - 1][1], saved[li - 1][2], H.ACT_RELU, G)
+                if d == "conv3_fwd_raw":
+                    dh = ops.conv3_fwd_raw(dy, wd, L.cin, 3, r.nslabs)
+                elif d == "conv3_dgrad_bwdstats":
+                    dh, bpart, bnb = ops.conv3_dgrad_bwdstats(dy, wd, L.cin, 3, prev.y, prev.stats, H.ACT_RELU, G)
                 else:
                     dh = ops.conv3_fwd(dy, wd, None, L.cin, 3)
             else:
-                kind = 0 if L.kind == "dw" else 1
                 _, bp = self.k2_packed(("k2", li), True)
-                sg = skip_grads.pop() if kind == 0 else None      # down conv: x_in is a skip source, the decoder-side gradient is joined in place
-                # (round 6) the layer in front has a pre-norm tensor of its own and no dropout epilogue: this dgrad's epilogue leaves its norm's
-                # backward statistics (bcp_down_dgrad_bwdstats / bcp_up_dgrad_bwdstats) where the shape is served -- no k_col_partial<1> pass over (y, da)
-                prev = saved[li - 1] if li > 0 else None
-                # (the epilogue rebuilds the ReLU pattern of the layer in front from z alone: not behind the closing layer of a residual block)
-                if (prev is not None and prev[1] is not None and prev[3] is None and not self._layers[li - 1].closing
-                        and ops.k2_bwdstat_rows(kind, dy.shape, L.cin, G) > 0):
-                    dh, bpart, bnb = ops.k2_dgrad_bwdstats(kind, dy, bp, L.cin, prev[1], prev[2], H.ACT_RELU, G, out=sg, accumulate=sg is not None)
-                elif kind == 0:
+                sg = skip_grads.pop() if L.kind == "dw" else None      # down conv: x_in is a skip source, the decoder-side gradient is joined in place
+                if d == "k2_dgrad_bwdstats":
+                    dh, bpart, bnb = ops.k2_dgrad_bwdstats(int(L.kind == "up"), dy, bp, L.cin, prev.y, prev.stats, H.ACT_RELU, G, out=sg,
+                                                           accumulate=sg is not None)
+                elif d == "down_dgrad":
                     dh = ops.down_dgrad(dy, bp, L.cin, out=sg, accumulate=True)
                 else:
                     dh = ops.up_dgrad(dy, bp, L.cin)
             if L.block_first and li > 0:
                 # the join: the block input's gradient = the first layer's dgrad + the shortcut's dres.  The joined tensor is what the layer in
                 # front consumes (and, behind an up layer, what skip_grads receives)
-                assert nsl == 1 and bpart is None
                 dh = ops.axpy(dh, dres, 1.0)
                 ops._no_amax(dh)
         flush_wgrads()
         self._join_wgrad_stream(dlogits)
         return None
+

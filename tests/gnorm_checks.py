@@ -344,7 +344,7 @@ def check_gn_pattern_grads(ops, dev, monkeypatch, variant="la", seed=11, N=2, bo
     loss = BU.sup_loss(out, tgt.to(dev))
     loss.backward()
     saved = net._last_saved
-    masks = [NC._pattern(s[1], s[2], s[4]) for s in saved[:-1]]
+    masks = [NC._pattern(s.y, s.stats, saved.G) for s in saved.layers]
     Pd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in P.items()}
     Q = O._with_grad(Pd, set(O.trainable_keys(Pd)))
     o64 = O.vnet_forward(Q, x.double(), dm, True, variant, act_masks=masks)

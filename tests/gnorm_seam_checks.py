@@ -22,7 +22,7 @@ case may have at most KINK_CAP of its elements there.
   F  every one of A .. E evaluates near-miss fp64 variants (per-channel in place of per-group statistics, sample n reading sample n-1's
      table, the k2 term dropped from dy, row 4's sign flipped in the conv-bias gradient, a neighbour channel's scale) against the SAME
      bound and asserts that it rejects them: no bound here can be vacuous
-  G  route_census            host-only row queries over the layer list of both V-Nets at the product shapes: every (producer, channels)
+  G  route_census            the network's planner (VNet.plan_forward / plan_backward, launch-free) for both V-Nets at the product shapes: every (producer, channels)
                              pair the product fuses has a case in B or C
 
 Inputs: a per-channel offset of order 30 with spread ~1 (the group variance of a layer with several channels per group is then dominated
@@ -505,12 +505,10 @@ FWD_SEAMS_GPU = (("up", 2, 32, 16, (16, 32, 32), ("res",)),)      # thousands of
 
 def fwd_rows(ops, prod, xshape, Cout, G):
     """the row query of the producer's fused forward statistics (host only, launches nothing)"""
-    N, D, Hh, W, Cin = xshape
     if prod == "c1":
-        return ops._ws_bytes("bcp_conv3_c1_stat_rows", N, D, Hh, W, 3, G)
+        return ops.conv3_c1_stat_rows(xshape, 3, G)
     if prod == "c3":
-        ws = ops._ws_bytes("bcp_conv3_fwd_workspace_bytes", N, D, Hh, W, Cin, Cout, 3)
-        return ops._ws_bytes("bcp_conv3_stat_rows", N, D, Hh, W, Cin, Cout, 3, G, 1 if ws else 0)
+        return ops.conv3_stat_rows(xshape, Cout, 3, G)
     return ops.k2_stat_rows(0 if prod == "down" else 1, xshape, Cout, G)
 
 
@@ -591,9 +589,8 @@ BWD_SEAMS_K2 = ((0, 2, 16, 32, (4, 8, 8)), (1, 2, 32, 16, (8, 16, 16)))
 
 
 def bwd_rows(ops, prod, dyshape, Cin, G):
-    N, D, Hh, W, Cout = dyshape
     if prod == "c3":
-        return ops._ws_bytes("bcp_conv3_bwdstat_rows", N, D, Hh, W, Cout, Cin, 3, G)
+        return ops.conv3_bwdstat_rows(dyshape, Cin, 3, G)
     return ops.k2_bwdstat_rows(0 if prod == "down" else 1, dyshape, Cin, G)
 
 
@@ -760,41 +757,23 @@ def covered_routes():
 
 
 def route_census(ops, verbose=True):
-    """walk the layer list of the GroupNorm V-Nets at the product shapes with groups = N (networks/VNet.py _forward_impl /
-    _backward_impl) and ask the library, launching nothing, which producers leave statistics rows there -> {(route, C): {(workload, N):
-    rows}} of the positive answers"""
+    """ask the network's own planner (networks/VNet.py plan_forward / plan_backward: shape queries of the library, no launch) for the routes
+    of the GroupNorm V-Nets' training step at the product shapes -> {(route, C): {(workload, N): rows}} of the producers that leave
+    statistics rows: a forward producer for its own norm (C = its output channels), a dgrad for the norm of the layer in front (its input
+    channels)"""
     from bcp_amd.networks.VNet import VNet
     found = {}
     for wl, (Ns, sp0) in CENSUS_SHAPES.items():
         variant = "pancreas" if wl == "pancreas" else "la"
-        net = VNet(n_channels=1, n_classes=2, normalization="groupnorm", has_dropout=variant == "la", variant=variant)
-        layers = net._layers
+        net = VNet(n_channels=1, n_classes=2, normalization="groupnorm", has_dropout=variant == "la", variant=variant).set_ops(ops)
         for N in Ns:
-            sp, shapes = tuple(sp0), []
-            for L in layers:                # the input extents of every layer
-                shapes.append(sp)
-                sp = tuple(e // 2 for e in sp) if L.kind == "dw" else tuple(2 * e for e in sp) if L.kind == "up" else sp
-            for li, L in enumerate(layers):
-                D, Hh, W = shapes[li]
-                xs = (N, D, Hh, W, L.cin)
-                prod = {"c1": "c1", "c3": "c3", "dw": "down", "up": "up"}[L.kind]
-                route = {"c1": "conv3_c1_fwd_stats", "c3": "conv3_fwd_stats", "down": "down_fwd_stats", "up": "up_fwd_stats"}[prod]
-                rows = fwd_rows(ops, prod, xs, L.cout, N)
-                if rows > 0:
-                    found.setdefault((route, L.cout), {})[(wl, N)] = rows
-                # backward: this layer's dgrad leaves the statistics of the layer in front when that one has no dropout epilogue
-                if li == 0 or layers[li - 1].drop is not None and variant == "la":
-                    continue
-                osp = tuple(e // 2 for e in shapes[li]) if L.kind == "dw" else tuple(2 * e for e in shapes[li]) if L.kind == "up" else shapes[li]
-                dys = (N,) + osp + (L.cout,)
-                if L.kind == "c3":
-                    rows, route = bwd_rows(ops, "c3", dys, L.cin, N), "conv3_dgrad_bwdstats"
-                elif L.kind in ("dw", "up"):
-                    rows, route = bwd_rows(ops, prod, dys, L.cin, N), prod + "_dgrad_bwdstats"
-                else:
-                    continue
-                if rows > 0:
-                    found.setdefault((route, L.cin), {})[(wl, N)] = rows
+            plan = net.plan_forward(N, *sp0, groups=1, save=True, training=True, dropout=net.has_dropout)
+            for L, r, b in zip(net._layers, plan.layers, net.plan_backward(plan)[1]):
+                k2 = {"dw": "down", "up": "up"}.get(L.kind)           # (Ops.k2_fwd_stats / k2_dgrad_bwdstats: one wrapper, two kernels)
+                if r.rows > 0:
+                    found.setdefault((k2 + "_fwd_stats" if k2 else r.producer, L.cout), {})[(wl, N)] = r.rows
+                if b.rows > 0:
+                    found.setdefault((k2 + "_dgrad_bwdstats" if k2 else b.dgrad, L.cin), {})[(wl, N)] = b.rows
     if verbose:
         for k in sorted(found):
             print(f"[gnorm-seam census] {k[0]} C={k[1]}: " + ", ".join(f"{wl} N={n}: {r}" for (wl, n), r in sorted(found[k].items())))

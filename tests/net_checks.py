@@ -1028,7 +1028,7 @@ def check_vnet_pattern_grads(ops, dev, variant="la", shape=(32, 32, 16), seed=11
     loss = BU.sup_loss(out, tgt.to(dev))
     loss.backward()
     saved = net._last_saved
-    masks = [_pattern(s[1], s[2], s[4]) for s in saved[:-1]]
+    masks = [_pattern(s.y, s.stats, saved.G) for s in saved.layers]
     Pd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in P.items()}
     Q = O._with_grad(Pd, set(O.trainable_keys(Pd)))
     o64 = O.vnet_forward(Q, x.double(), dm, True, variant, act_masks=masks)
@@ -1061,7 +1061,7 @@ def check_vnet_features(ops, dev, shape=(48, 48, 48)):
     net._keep_saved = True                     # (also keeps this call on the eager path)
     out, feat = net(x)
     idx5 = max(i for i, L in enumerate(net._layers) if L.name.startswith("block_five."))
-    x5 = net._last_saved[idx5 + 1][0]           # input of block_five_up = x5 after Dropout3d, channels-last
+    x5 = net._last_saved.layers[idx5 + 1].x           # input of block_five_up = x5 after Dropout3d, channels-last
     ref = F.max_pool3d(x5.permute(0, 4, 1, 2, 3), 3, stride=2)
     assert tuple(feat.shape) == (2, 256) + tuple((s // 16 - 3) // 2 + 1 for s in shape), tuple(feat.shape)
     assert torch.equal(feat.contiguous().cpu(), ref.contiguous().cpu())

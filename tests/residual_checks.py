@@ -535,17 +535,17 @@ def check_res_golden_tiny(ops, dev):
     assert int(sd["encoder.block_one.conv.1.num_batches_tracked"]) == 1
 
 
-def _pattern(net, li, s):
+def _pattern(net, li, s, G):
     """activation pattern of layer li from what the HIP forward saved; a closing layer's is z + r > 0, rebuilt from the saved y, the table
     and the block input"""
-    y, stats, G = s[1], s[2], s[4]
+    y, stats = s.y, s.stats
     N, C = y.shape[0], y.shape[-1]
     st = stats.view(5, G, C)
     gi = torch.arange(N, device=y.device) // (N // G)
     shp = (N, 1, 1, 1, C)
     z = (y - st[0][gi].view(shp)) * st[2][gi].view(shp) + st[3][gi].view(shp)
     if net._layers[li].closing:
-        z = z + s[5]
+        z = z + s.r_in
     return (z > 0).permute(0, 4, 1, 2, 3).cpu()
 
 
@@ -564,7 +564,7 @@ def check_res_pattern_grads(ops, dev, seed=11, N=2, bound=1e-4):
     loss = BU.sup_loss(out, tgt.to(dev))
     loss.backward()
     saved = net._last_saved
-    masks = [_pattern(net, li, s) for li, s in enumerate(saved[:-1])]
+    masks = [_pattern(net, li, s, saved.G) for li, s in enumerate(saved.layers)]
     Pd = {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in P.items()}
     Q = O._with_grad(Pd, set(O.trainable_keys(Pd)))
     o64 = res_vnet_forward(Q, x.double(), dm, True, act_masks=masks)
@@ -691,8 +691,21 @@ class _Spy:
         setattr(self._ops, name, value)
 
 
-NORM_FWD = ("norm_fwd", "norm_fwd_res", "norm_fwd_slabs", "conv3_c1_norm_fwd", "up_fwd_norm", "norm_eval", "norm_eval_res")
-NORM_BWD = ("norm_bwd", "norm_bwd_res", "norm_bwd_slabs", "conv3_c1_norm_bwd", "conv3_c1_norm_bwd_wgrad", "up_norm_bwd", "pw16_bwd_norm_bwd")
+NORM_FWD = ("norm_fwd", "norm_fwd_res", "norm_fwd_slabs", "conv3_c1_norm_fwd", "up_fwd_norm", "norm_eval", "norm_eval_res", "gnorm_fwd")
+NORM_BWD = ("norm_bwd", "norm_bwd_res", "norm_bwd_slabs", "conv3_c1_norm_bwd", "conv3_c1_norm_bwd_wgrad", "up_norm_bwd", "pw16_bwd_norm_bwd", "gnorm_bwd")
+PRODUCERS = ("conv3_c1_fwd_stats", "conv3_c1_fwd", "conv3_fwd_raw", "conv3_fwd_stats", "conv3_fwd", "k2_fwd_stats", "down_fwd", "up_fwd")
+
+
+def planned_routes(net, plan, backward=True):
+    """what the network's planner (VNet.plan_forward / plan_backward) returned for a pass, in _routes' vocabulary: per layer [forward norm op
+    (+ ':stats_only'), backward norm op (+ ':partial'), a *_dgrad_bwdstats epilogue takes this layer's backward statistics], the producer
+    ops and the head's ops"""
+    head, bw = net.plan_backward(plan) if backward else (None, None)
+    routes = [[r.norm + (":stats_only" if r.stats_only else ""), None, False] for r in plan.layers]
+    for li, b in enumerate(bw or ()):
+        routes[li][1] = b.norm + (":partial" if b.partial else "")
+        routes[li][2] = li + 1 < len(bw) and bw[li + 1].rows > 0
+    return routes, [r.producer for r in plan.layers], [plan.head] + ([head] if backward else [])
 
 
 def _routes(ops, dev, has_residual):
@@ -730,6 +743,9 @@ def _routes(ops, dev, has_residual):
             assert len(hit) == 1, (n, hit)
             routes[hit[0]][2] = True
     head = [n for n, a, k, r in spy.log if n.startswith("pw16_")]
+    # what ran is what the planner returned for this pass
+    planned, _, phead = planned_routes(net, net.plan_call(2, *NET_SHAPE, save=True))
+    assert routes == planned and head == phead, ("ran != planned", [(L.name, r, p) for L, r, p in zip(net._layers, routes, planned) if r != p], head, phead)
     return net, routes, head
 
 
@@ -756,3 +772,97 @@ def check_res_routes(ops, dev):
             assert r[1:] == p[1:], (L.name, "backward route", r, p)
     assert nclosing == 9
     return res, plain
+
+
+# ------------------------------------------------------------------------------------------ planned == ran, every configuration
+# (normalization, variant, has_residual, mode).  train: a saving forward and its backward; eval: model.eval() under no_grad; teacher: training
+# mode under no_grad with groups=2, as the self-training steps run the EMA network
+PLAN_CASES = {"la-bn-train": ("batchnorm", "la", False, "train"), "la-res-train": ("batchnorm", "la", True, "train"),
+              "la-gn-train": ("groupnorm", "la", False, "train"), "pancreas-in-train": ("instancenorm", "pancreas", False, "train"),
+              "pancreas-gn-train": ("groupnorm", "pancreas", False, "train"), "la-bn-eval": ("batchnorm", "la", False, "eval"),
+              "la-res-eval": ("batchnorm", "la", True, "eval"), "la-bn-teacher": ("batchnorm", "la", False, "teacher")}
+
+
+def _plan_case_net(case, dev, ops):
+    from bcp_amd.networks.VNet import VNet
+    norm, variant, res, mode = PLAN_CASES[case]
+    torch.manual_seed(7)
+    net = VNet(n_channels=1, n_classes=2, normalization=norm, has_dropout=variant == "la", has_residual=res, variant=variant).to(dev)
+    net.flatten_()
+    net.use_plans = False
+    net.train(mode != "eval")
+    net._groups = 2 if mode == "teacher" else 1
+    return net.set_ops(ops), mode
+
+
+def observed_routes(log, nlayers):
+    """the spy's log of one pass, by call order (every layer calls one forward norm op, behind its producer if it has one of its own, and
+    in a backward pass one backward norm op, in reverse order) -> planned_routes' three values"""
+    routes, prods, prod, nb = [], [], None, 0
+    for n, a, k, r in log:
+        if n in NORM_FWD:
+            routes.append([n + (":stats_only" if k.get("stats_only") else ""), None, False])
+            prods.append(prod or n)
+            prod = None
+        elif n in PRODUCERS and len(routes) < nlayers:
+            assert prod is None, (prod, n)
+            prod = n
+        elif n in NORM_BWD:
+            nb += 1
+            routes[nlayers - nb][1] = n + (":partial" if k.get("partial") is not None else "")
+        elif n.endswith("_dgrad_bwdstats") and r[2] > 0:
+            routes[nlayers - nb - 1][2] = True
+    assert len(routes) == nlayers and nb in (0, nlayers), (len(routes), nb)
+    return routes, prods, [n for n, a, k, r in log if n.startswith("pw16_")]
+
+
+def check_planned_equals_ran(ops, dev, case):
+    """one pass of the network of PLAN_CASES[case] at NET_SHAPE, N = 2, under the spy: every layer's producer, forward norm op, stats_only,
+    backward norm op, partial and bwdstats epilogue, and the head's ops, are what the planner returned for that pass"""
+    spy = _Spy(ops)
+    net, mode = _plan_case_net(case, dev, spy)
+    if dev.type == "cpu":
+        BU.set_test_ops(ops)
+    rng = np.random.default_rng(3)
+    x = torch.from_numpy(rng.standard_normal((2, 1) + NET_SHAPE, dtype=np.float32)).to(dev)
+    if mode == "train":
+        BU.sup_loss(net(x)[0], torch.from_numpy(rng.integers(0, 2, (2,) + NET_SHAPE)).to(dev)).backward()
+    else:
+        with torch.no_grad():
+            net(x, groups=net._groups)
+    ran = observed_routes(list(spy.log), len(net._layers))
+    planned = planned_routes(net, net.plan_call(2, *NET_SHAPE, save=mode == "train"), backward=mode == "train")
+    assert ran == planned, (case, [(L.name, r, p) for L, r, p in zip(net._layers, ran[0], planned[0]) if r != p], ran[1:], planned[1:])
+    return ran
+
+
+# every route name the cases above reach at NET_SHAPE (32, 32, 16), N = 2, on the simulator and on the gfx950 library alike (the deep levels
+# have <= 4096 rows per group, so the slab routes are in).  NOT reached, because the library's row queries answer by size; each of them is
+# planned at product size against the product-op table in tests/test_plan_product.py:
+#   up_fwd_norm / up_norm_bwd          bcp_up_norm_rows: the recomputing transposed conv is served for large outputs only (DESIGN.md: 2^24 elements)
+#   k2_fwd_stats / k2_dgrad_bwdstats   bcp_k2_stat_rows / bcp_k2_bwdstat_rows: the k2 GEMMs' statistics epilogues, large outputs only as well
+#   conv3_c1_norm_bwd                  only with the measurement switch BCP_C1_BWD_FUSED=0
+ROUTES_REACHED = {
+    "conv3_c1_norm_fwd", "conv3_c1_fwd_stats", "conv3_c1_fwd", "conv3_fwd_raw", "conv3_fwd_stats", "conv3_fwd", "down_fwd", "up_fwd",
+    "norm_fwd", "norm_fwd:stats_only", "norm_fwd_slabs", "norm_fwd_res", "norm_eval", "norm_eval_res", "gnorm_fwd", "gnorm_fwd:stats_only",
+    "pw16_fwd", "pw16_fwd_norm", "pw16_bwd", "pw16_bwd_norm", "pw16_bwd_norm_bwd",
+    "norm_bwd", "norm_bwd:partial", "norm_bwd_slabs", "norm_bwd_res", "gnorm_bwd", "gnorm_bwd:partial", "conv3_c1_norm_bwd_wgrad",
+    "conv3_dgrad_bwdstats", "down_dgrad", "up_dgrad"}
+
+
+def routes_reached(ops):
+    """the planner alone (no launch) over PLAN_CASES: the set of producer / norm / head / backward names -- check_planned_equals_ran shows
+    case by case that these are the ops that ran"""
+    names = set()
+    for case in PLAN_CASES:
+        net, mode = _plan_case_net(case, torch.device("cpu"), ops)
+        routes, prods, head = planned_routes(net, net.plan_call(2, *NET_SHAPE, save=mode == "train"), backward=mode == "train")
+        names |= set(prods) | set(head) | {n for r in routes for n in r[:2] if n}
+        if mode == "train":
+            names |= {b.dgrad for b in net.plan_backward(net.plan_call(2, *NET_SHAPE, save=True))[1] if b.dgrad}
+    return names
+
+
+def check_routes_reached(ops):
+    got = routes_reached(ops)
+    assert got == ROUTES_REACHED, (sorted(got - ROUTES_REACHED), sorted(ROUTES_REACHED - got))

@@ -105,6 +105,22 @@ def test_res_eval(emu_ops):
     R.check_res_eval(emu_ops, CPU)
 
 
+@pytest.mark.extended
+@pytest.mark.parametrize("case", sorted(R.PLAN_CASES))
+def test_planned_equals_ran(emu_ops, case):
+    R.check_planned_equals_ran(emu_ops, CPU, case)
+
+
+def test_routes_reached(emu_ops):
+    R.check_routes_reached(emu_ops)
+
+
+def test_routes_reached_product_library():
+    """the gfx950 library's shape queries give the same set: no GPU needed"""
+    assert os.path.exists(_lib.LIB_PATH), "libbcp_hip.so missing -- run __graft_entry__.build()"
+    R.check_routes_reached(Ops(_lib.Binding(_lib.LIB_PATH), allow_cpu=True))
+
+
 def test_refused_configurations():
     from bcp_amd.networks.VNet import VNet
     for kw in (dict(normalization="groupnorm"), dict(normalization="instancenorm", variant="pancreas")):

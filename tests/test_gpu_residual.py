@@ -96,6 +96,11 @@ def test_res_routes(gpu_ops, dev):
     R.check_res_routes(gpu_ops, dev)
 
 
+@pytest.mark.parametrize("case", sorted(R.PLAN_CASES))
+def test_planned_equals_ran(gpu_ops, dev, case):
+    R.check_planned_equals_ran(gpu_ops, dev, case)
+
+
 # ---- step and plans
 def test_res_step(gpu_ops, dev, monkeypatch):
     R.check_res_step(gpu_ops, dev, monkeypatch)
