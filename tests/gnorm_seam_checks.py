@@ -24,6 +24,16 @@ case may have at most KINK_CAP of its elements there.
      bound and asserts that it rejects them: no bound here can be vacuous
   G  route_census            the network's planner (VNet.plan_forward / plan_backward, launch-free) for both V-Nets at the product shapes: every (producer, channels)
                              pair the product fuses has a case in B or C
+  H  check_own_blocks        the kernels' OWN statistics passes at 2 .. 130 blocks per sample (A .. E leave 1 or 2): ragged last chunk, a
+     check_apply_past_cap    block with one row, a block with none; reduce_partials' four-way walk and tail on kernel-made rows at N > 1;
+                             the workspace layout partial | terms | coef with more than one row; the apply passes' unrolled trips and
+                             remainder loops.  (a) elementwise against fp64 as B / C / E, ReLU and none, accumulate both ways; (b) the
+                             scratch buffer filled with 0x7f bytes in front of both calls: every output keeps its bits; (c) sample 1 alone
+                             changed: the other samples' a, table and dy keep their bits; (d) statistics that miss one whole block are
+                             rejected by the same bound; (e) norm_apply_cap = 2 (one workgroup per sample: hundreds of unrolled trips, then
+                             the remainder loop): bit for bit the default launch, and -- device only -- N = 4 at 52 x 52 x 50 x 16, a sample
+                             longer than one unrolled trip of the library's own grid cap; (f) KINK_CAP on every reference.  The simulator
+                             runs every case of OWN_BLOCK_CASES; check_apply_past_cap (8.7 M elements) is left to the device
 
 Inputs: a per-channel offset of order 30 with spread ~1 (the group variance of a layer with several channels per group is then dominated
 by the differences BETWEEN channels, and a channel reading its neighbour's statistics is off by whole units), per-channel scales, and
@@ -56,6 +66,10 @@ figures; an MI355X gave the same to two digits except where a second figure stan
   D  logits 0.011, dh 0.0016, dw 0.0013, db 0.00007 x TAU
   E  forward 0.28, dy 0.28, dgamma 0.46, dbeta 0.001, bias_chain 0.011 x TAU (worst: one or two rows per sample)
   B on the device only: up 32 -> 16 at coarse 16 x 32 x 32 (row blocks per workgroup R > 1) stays below the 0.35 of the small case.
+  H  forward 0.024, dy 0.0018, bias_chain 0.0058 x TAU; bias against the fp64 sum of dy 2.3 x 2^-22 cond_c (measured only, as in E); past the
+     apply cap (device) forward 0.030, dy 0.0019 x TAU; largest kink share 5.0e-6 (cap 1e-4).  One whole block left out of the statistics
+     (measured on the fp64 reference alone): 3.6e-4 .. 6.9e-4 x cond at the three 129- / 130-block shapes, 5.1e-4 .. 4.7e-2 at the others,
+     against TAU = 6.1e-5.  Leaving out only the one-row block of the 130-block shape is inside the bound (5.2e-5): (b) is what catches it.
 """
 import numpy as np
 import torch
@@ -103,9 +117,14 @@ def _group_mean(t, cg):
 
 def _stats64(y3, how="group"):
     """(mean, var) as [N, 1, C] of a [N, n, C] fp64 tensor.  how: 'group' -- nn.GroupNorm(16, C); the near-misses 'channel' (every
-    channel its own statistics) and 'shift' (sample n reads sample n - 1's)"""
+    channel its own statistics), 'shift' (sample n reads sample n - 1's) and ('drop', r0, r1) (rows r0 .. r1 - 1, one block of the
+    statistics pass, left out of every sum and of the count)"""
     N, n, C = y3.shape
     cg = C // GROUPS
+    if isinstance(how, tuple):
+        yk = torch.cat((y3[:, :how[1]], y3[:, how[2]:]), 1)
+        mu = _group_mean(yk, cg)
+        return mu, _group_mean((yk - mu) ** 2, cg)
     if how == "channel":
         mu = y3.mean(1, keepdim=True)
         return mu, ((y3 - mu) ** 2).mean(1, keepdim=True)
@@ -116,14 +135,15 @@ def _stats64(y3, how="group"):
     return mu, var
 
 
-def gn_ref64(y, gamma, beta, act, eps=EPS, how="group"):
+def gn_ref64(y, gamma, beta, act, eps=EPS, how="group", stats=None):
     """fp64 nn.GroupNorm(16, C) + activation of a channels-last tensor [N, ..., C]: product_ops.norm_ref64 with groups of C / 16 adjacent
-    channels per sample -> (a, z, xhat, mean_g [N, 16], var_g [N, 16], cond), cond = |gamma| (|xhat| + 1) + |beta|"""
+    channels per sample -> (a, z, xhat, mean_g [N, 16], var_g [N, 16], cond), cond = |gamma| (|xhat| + 1) + |beta|.  stats: (mean, var) as
+    _stats64 returns them, in place of y's own (a caller that walks the samples one by one and wants a neighbour's)"""
     y = y.detach().double().cpu()
     N, C = y.shape[0], y.shape[-1]
     cg = C // GROUPS
     y3 = y.reshape(N, -1, C)
-    mu, var = _stats64(y3, how)
+    mu, var = _stats64(y3, how) if stats is None else stats
     xh = ((y3 - mu) / torch.sqrt(var + eps)).reshape(y.shape)
     gm = torch.ones(C, dtype=torch.float64) if gamma is None else gamma.detach().double().cpu()
     bt = torch.zeros(C, dtype=torch.float64) if beta is None else beta.detach().double().cpu()
@@ -138,14 +158,14 @@ class BwdRef:
     log2(cg * rows) on the two group means; inf at kink elements), the allowance a kink element's term has in every other element's
     group means, dz / xhat / dk as [N, n, C], and the conv-bias gradient with its chain cond and kink allowance"""
 
-    def __init__(self, y, gamma, beta, act, da64, mult=None, how="group", drop_k2=False, eps=EPS):
+    def __init__(self, y, gamma, beta, act, da64, mult=None, how="group", drop_k2=False, eps=EPS, stats=None):
         ys = tuple(y.shape)
         N, C = ys[0], ys[-1]
         cg = C // GROUPS
-        _, z, xh, _, _, fcond = gn_ref64(y, gamma, beta, act, eps, how)
+        _, z, xh, _, _, fcond = gn_ref64(y, gamma, beta, act, eps, how, stats)
         y3 = y.detach().double().cpu().reshape(N, -1, C)
         rows = y3.shape[1]
-        mu, var = _stats64(y3, how)
+        mu, var = _stats64(y3, how) if stats is None else stats
         rstd = 1.0 / torch.sqrt(var + eps)
         kink = _kink(z, fcond) if act else torch.zeros_like(z, dtype=torch.bool)      # (no activation: no branch to flip)
         _, dact = _acts(act, z)
@@ -304,6 +324,16 @@ def _fwd_check(ops, dev, tag, seam, y, gamma, beta, act, cs=None, res=None, part
     return a, st
 
 
+def _grad_start(rng, C, accumulate, dev):
+    """(dgamma, dbeta, dbias) before a backward call -> (the values the result adds to, the device buffers).  accumulate: non-zero
+    starting values that differ per channel; otherwise the kernel must overwrite whatever the buffers held"""
+    if accumulate:
+        g0 = [torch.from_numpy((rng.standard_normal(C) * s + o).astype(np.float32)) for s, o in ((3.0, 1.0), (3.0, -2.0), (3.0, 0.5))]
+    else:
+        g0 = [torch.zeros(C) for _ in range(3)]
+    return g0, [t.clone().to(dev) if accumulate else torch.full((C,), 7.0).to(dev) for t in g0]
+
+
 def _bwd_check(ops, dev, tag, seam, y, gamma, beta, act, da, st, cs=None, partial=None, nb=0, accumulate=False, rng=None, nearmiss=True,
                ref=None, edges=False):
     """gnorm_bwd (backward statistics from `partial` or the kernel's own pass) against fp64: dy elementwise, dgamma / dbeta as
@@ -313,12 +343,7 @@ def _bwd_check(ops, dev, tag, seam, y, gamma, beta, act, da, st, cs=None, partia
     cg = C // GROUPS
     ref = BwdRef(y, gamma, beta, act, da.double().cpu(), _mult(cs, tuple(y.shape))) if ref is None else ref
     _kink_cap(tag, ref.kink)
-    if accumulate:
-        g0 = [torch.from_numpy((rng.standard_normal(C) * s + o).astype(np.float32)) for s, o in ((3.0, 1.0), (3.0, -2.0), (3.0, 0.5))]
-    else:
-        g0 = [torch.zeros(C) for _ in range(3)]
-    # (not accumulating: the kernel must overwrite whatever the buffers held)
-    gr = [t.clone().to(dev) if accumulate else torch.full((C,), 7.0).to(dev) for t in g0]
+    g0, gr = _grad_start(rng, C, accumulate, dev)
     csd = None if cs is None else cs.to(dev)
     kw = dict(partial=partial, nb=nb) if partial is not None else {}
     dy = ops.gnorm_bwd(y.to(dev), da.to(dev), st, gamma.to(dev), act, gr[0], gr[1], gr[2], accumulate, chan_scale=csd, **kw)
@@ -512,8 +537,9 @@ def fwd_rows(ops, prod, xshape, Cout, G):
     return ops.k2_stat_rows(0 if prod == "down" else 1, xshape, Cout, G)
 
 
-def _produce(ops, dev, rng, prod, N, Cin, Cout, sp, tag):
-    """the producer's plain launch and its *_fwd_stats launch on one input, bias of order 30 per channel -> (y, partial, rows)"""
+def _produce(ops, dev, rng, prod, N, Cin, Cout, sp, tag, verify=True):
+    """the producer's plain launch and its *_fwd_stats launch on one input, bias of order 30 per channel -> (y, partial, rows).  verify
+    False (the product-op drivers, whose producer rows have checks of their own): the *_fwd_stats launch alone"""
     x = K.to_cl(K.R(rng, N, Cin, *sp)) * torch.tensor(SAMPLE_SCALE[:N]).view(N, 1, 1, 1, 1) + torch.tensor(SAMPLE_OFF[:N]).view(N, 1, 1, 1, 1)
     xd = PO._amax(H, x.contiguous().to(dev), dev)             # (the networks' operands carry their |max|)
     b = (K.R(rng, Cout) * 0.1 + 30.0 * (1.0 + 0.03 * K.R(rng, Cout))).to(dev)
@@ -521,19 +547,21 @@ def _produce(ops, dev, rng, prod, N, Cin, Cout, sp, tag):
     assert rows > 0, f"{tag}: the row query serves no fused statistics here ({rows}): the seam is not covered"
     if prod == "c1":
         w = (K.R(rng, 16, 1, 3, 3, 3) * 0.2).to(dev)
-        y0 = ops.conv3_c1_fwd(xd, w, b, 3).clone()
+        y0 = ops.conv3_c1_fwd(xd, w, b, 3).clone() if verify else None
         y, part, nb = ops.conv3_c1_fwd_stats(xd, w, b, 3, N)
     elif prod == "c3":
         wf, _ = ops.conv3_pack((K.R(rng, Cout, Cin, 3, 3, 3) * 0.1).to(dev).contiguous(), 3)
-        y0 = ops.conv3_fwd(xd, wf, b, Cout, 3).clone()
+        y0 = ops.conv3_fwd(xd, wf, b, Cout, 3).clone() if verify else None
         y, part, nb = ops.conv3_fwd_stats(xd, wf, b, Cout, 3, N)
     else:
         kind = 0 if prod == "down" else 1
         w = (K.R(rng, Cout, Cin, 2, 2, 2) if kind == 0 else K.R(rng, Cin, Cout, 2, 2, 2)) * 0.1
         bp = ops.k2_pack(w.to(dev), Cin, Cout, H.PACK_DOWN_FWD if kind == 0 else H.PACK_UP_FWD)
-        y0 = (ops.down_fwd if kind == 0 else ops.up_fwd)(xd, bp, b, Cout).clone()
+        y0 = (ops.down_fwd if kind == 0 else ops.up_fwd)(xd, bp, b, Cout).clone() if verify else None
         y, part, nb = ops.k2_fwd_stats(kind, xd, bp, b, Cout, N)
     assert nb == rows, (tag, nb, rows)
+    if not verify:
+        return y, part, rows
     assert torch.equal(_bits(y), _bits(y0)), f"{tag}: y differs from the plain launch"
     # the partial rows against fp64 sums of the kernel's own y, per (sample, channel)
     pt = _partials(part, N, rows, Cout)
@@ -726,6 +754,162 @@ def check_own_pass_edges(ops, dev):
         da = (K.to_cl(K.R(rng, N, C, *sp)) + 5.0).contiguous()
         for accumulate in (False, True):
             _bwd_check(ops, dev, tag + f" accumulate={accumulate}", "E own bwd", y, gamma, beta, act, da, st, cs=cs, accumulate=accumulate, rng=rng, nearmiss=nm, edges=True)
+
+
+# ------------------------------------------------------------------------------------------ H. the own passes at many blocks per sample
+def own_geometry(rows, C):
+    """the launch geometry of the kernels' own statistics passes, from csrc/norm.hip: norm_blocks = clamp(rows C / 16384, 1, 1024) blocks
+    per sample, k_col_partial's chunk = ceil(rows / nb) rows per block -> (nb, chunk, rows of the ragged block behind the full ones or 0,
+    trailing blocks without a row)"""
+    nb = max(1, min(1024, rows * C // 16384))
+    chunk = -(-rows // nb)
+    full, last = divmod(rows, chunk)
+    return nb, chunk, last, nb - full - (1 if last else 0)
+
+
+def apply_blocks(rows, C, N, cap=2048):
+    """apply_grid of csrc/norm.hip for one sample's rows C / 4 float4: 1024 float4 per block and unrolled trip, at most cap / N blocks"""
+    return max(1, min(-(-(rows * (C // 4)) // 1024), max(1, cap // N)))
+
+
+# (N, C, spatial extents, nb, rows of the ragged block, blocks without a row, also run with norm_apply_cap = 2): nb hits 2, 33, 97 (the
+# 32-slot tree alone; its tail; ONE slot in the four-way loop of reduce_partials), 129 and 130 (every slot in the four-way loop, one / two
+# slots in its tail), every width 16 .. 256.  rows = nb 16384 / C plus an odd remainder
+OWN_BLOCK_CASES = (
+    (3, 256, (1, 53, 157), 130, 1, 1, True),        # block 128 has exactly one row, block 129 none
+    (2, 16, (1, 1, 132133), 129, 933, 0, True),
+    (3, 64, (1, 7, 4733), 129, 235, 0, False),
+    (2, 32, (1, 1, 1061), 2, 530, 0, False),
+    (2, 32, (1, 3, 5645), 33, 487, 0, False),
+    (2, 32, (1, 1, 49795), 97, 451, 0, False),
+    (2, 128, (1, 1, 309), 2, 154, 0, False),
+    (2, 128, (1, 11, 391), 33, 109, 0, False),
+    (2, 128, (1, 5, 2503), 97, 35, 0, False),
+)
+# the simulator runs every case (the largest takes it about as long as its fp64 references take the host)
+PAST_CAP_CASE = (4, 16, (52, 52, 50))       # device only: 8.7 M elements
+
+
+class _Scratch:
+    """ops whose gnorm_fwd / gnorm_bwd find the grow-only scratch buffer they are about to use filled with `byte`.  0x7f: every double of
+    the partial rows, the terms and every float of the coefficients is finite and huge (1.4e306 / 3.4e38) -- a trailing block that leaves
+    its row unwritten, or a finalize that reads past the rows of its sample, shows in every output"""
+
+    def __init__(self, ops, byte):
+        self.ops, self.byte = ops, byte
+
+    def _fill(self, y):
+        N, C = y.shape[0], y.shape[-1]
+        nbytes = self.ops._ws_bytes("bcp_gnorm_workspace_bytes", N, y.numel() // (N * C), C)
+        self.ops.workspace("gnorm", nbytes, y).fill_(self.byte)
+
+    def gnorm_fwd(self, y, *a, **kw):
+        self._fill(y)
+        return self.ops.gnorm_fwd(y, *a, **kw)
+
+    def gnorm_bwd(self, y, *a, **kw):
+        self._fill(y)
+        return self.ops.gnorm_bwd(y, *a, **kw)
+
+
+def _amax_of(t):
+    """the published |max| of a tensor (the slots between the strided values are not the kernels' to define)"""
+    return torch.tensor([H.amax_value(t._bcp_amax)])
+
+
+def _same_bits(tag, what, got, want):
+    assert torch.equal(_bits(got), _bits(want)), f"{tag}: {what} changed its bits"
+
+
+def _raw_step(ops, dev, y, da, gamma, beta, act, accumulate, cs=None):
+    """gnorm_fwd + gnorm_bwd on their own passes, no reference -> every output, for the bit comparisons of H.  The gradients start from
+    the values _bwd_check starts them from"""
+    g0, gr = _grad_start(np.random.default_rng(72), y.shape[-1], accumulate, dev)
+    yd, gd, csd = y.to(dev), gamma.to(dev), None if cs is None else cs.to(dev)
+    a, st = ops.gnorm_fwd(yd, gd, beta.to(dev), act, chan_scale=csd)
+    dy = ops.gnorm_bwd(yd, da.to(dev), st, gd, act, gr[0], gr[1], gr[2], accumulate, chan_scale=csd)
+    return dict(a=a, table=st, a_amax=_amax_of(a), dy=dy, dy_amax=_amax_of(dy), dgamma=gr[0], dbeta=gr[1], dbias=gr[2])
+
+
+def check_own_blocks(ops, dev, case):
+    """H (a) .. (f) for one shape of OWN_BLOCK_CASES: no partial= anywhere, every row is the kernels' own"""
+    N, C, sp, nb_x, last_x, empty_x, wrap = case
+    rows = sp[0] * sp[1] * sp[2]
+    nb, chunk, last, empty = own_geometry(rows, C)
+    assert (nb, last, empty) == (nb_x, last_x, empty_x), (case, nb, chunk, last, empty)
+    # the library sizes partial | terms | coef for this many rows per sample
+    assert ops._ws_bytes("bcp_gnorm_workspace_bytes", N, rows, C) == (N * nb * C * 2 + 3 * N * C) * 8 + 2 * N * C * 4, case
+    rng = np.random.default_rng(71)
+    y = _pre_norm(rng, N, sp, C)
+    gamma, beta = _affine(rng, C)
+    da = (K.to_cl(K.R(rng, N, C, *sp)) + 5.0).contiguous()
+    y1, da1 = y.clone(), da.clone()         # (c): sample 1 alone changed
+    y1[1] = y[1].flip(0, 1, 2) * 1.25 - 3.0
+    da1[1] = -da[1].flip(2)
+    full = (rows // chunk)
+    drops = (("block 0 left out of the statistics", ("drop", 0, chunk)),
+             ("the last full block left out of the statistics", ("drop", (full - 1) * chunk, full * chunk)))
+    zero, poison = _Scratch(ops, 0x00), _Scratch(ops, 0x7f)
+    for act in (H.ACT_RELU, 0):
+        tag = f"own blocks N={N} C={C} rows={rows} nb={nb} act={act}"
+        nm = act != 0                       # (the near-misses of the shared checks once per shape: they are the references' cost)
+        a, st = _fwd_check(zero, dev, tag, "H fwd", y, gamma, beta, act, nearmiss=nm)
+        # (d) the same bound, the same inputs: statistics that miss one whole block
+        ar, _, _, _, _, cond = gn_ref64(y, gamma, beta, act)
+        for what, how in drops:
+            r = _ratio(gn_ref64(y, gamma, beta, act, how=how)[0], ar, cond)
+            _rejects(tag, what, r)
+            print(f"[gnorm-seam] {tag}: {what}: {r:.3g} x cond (TAU {TAU:.3g})")
+        del ar, cond
+        ref = BwdRef(y, gamma, beta, act, da.double())
+        print(f"[gnorm-seam] {tag}: kink share {float(ref.kink.sum()) / ref.kink.numel():.3g}")
+        _note("H kink share (of KINK_CAP)", float(ref.kink.sum()) / ref.kink.numel() / KINK_CAP)
+        for accumulate in (False, True):
+            t = f"{tag} accumulate={accumulate}"
+            dy, _, gr = _bwd_check(zero, dev, t, "H bwd", y, gamma, beta, act, da, st, accumulate=accumulate, rng=np.random.default_rng(72),
+                                   nearmiss=nm and not accumulate, ref=ref)
+            base = dict(a=a, table=st, a_amax=_amax_of(a), dy=dy, dy_amax=_amax_of(dy), dgamma=gr[0], dbeta=gr[1], dbias=gr[2])
+            # (b) the scratch buffer full of 0x7f bytes in front of both calls
+            for k, v in _raw_step(poison, dev, y, da, gamma, beta, act, accumulate).items():
+                _same_bits(t + " [scratch poisoned]", k, v, base[k])
+            # (e) the apply passes in one or two workgroups: hundreds of unrolled trips per thread, then the remainder loop
+            if wrap:
+                assert apply_blocks(rows, C, N) > 4 * apply_blocks(rows, C, N, 2), case
+                ops.set_option("norm_apply_cap", "2")
+                try:
+                    wrapped = _raw_step(ops, dev, y, da, gamma, beta, act, accumulate)
+                finally:
+                    ops.set_option("norm_apply_cap", "")
+                for k, v in wrapped.items():
+                    _same_bits(t + " [norm_apply_cap = 2]", k, v, base[k])
+        # (c) the other samples keep their bits when sample 1 changes
+        other = _raw_step(ops, dev, y1, da1, gamma, beta, act, False)
+        base = _raw_step(ops, dev, y, da, gamma, beta, act, False)
+        assert not torch.equal(_bits(other["table"][:2, 1]), _bits(base["table"][:2, 1])), tag
+        for n in range(N):
+            if n != 1:
+                _same_bits(tag + f" [sample 1 changed] sample {n}", "a", other["a"][n], base["a"][n])
+                _same_bits(tag + f" [sample 1 changed] sample {n}", "table", other["table"][:, n], base["table"][:, n])
+                _same_bits(tag + f" [sample 1 changed] sample {n}", "dy", other["dy"][n], base["dy"][n])
+
+
+def check_apply_past_cap(ops, dev):
+    """H (e), second half: a sample longer than one unrolled trip of the library's own grid cap.  N = 4: 2048 / 4 = 512 blocks, 512 * 256 * 4
+    = 524 288 float4 per unrolled trip against 540 800 per sample -- every thread makes one unrolled trip, 16 512 of them one more in the
+    remainder loop, in k_norm_apply and in k_gnorm_bwd_apply; 132 statistics blocks per sample, with a channel scale"""
+    N, C, sp = PAST_CAP_CASE
+    rows = sp[0] * sp[1] * sp[2]
+    nv, grid = rows * (C // 4), apply_blocks(rows, C, N)
+    assert grid == 2048 // N and 4 * grid * 256 < nv < 5 * grid * 256, (nv, grid)
+    rng = np.random.default_rng(73)
+    y = _pre_norm(rng, N, sp, C)
+    gamma, beta = _affine(rng, C)
+    cs = _chan_scale(rng, N, C)
+    da = (K.to_cl(K.R(rng, N, C, *sp)) + 5.0).contiguous()
+    for act, accumulate in ((H.ACT_RELU, False), (0, True)):
+        tag = f"past the apply cap N={N} C={C} rows={rows} act={act} accumulate={accumulate}"
+        _, st = _fwd_check(ops, dev, tag, "H past cap fwd", y, gamma, beta, act, cs, nearmiss=act != 0)
+        _bwd_check(ops, dev, tag, "H past cap bwd", y, gamma, beta, act, da, st, cs=cs, accumulate=accumulate, rng=rng, nearmiss=False)
 
 
 # ------------------------------------------------------------------------------------------ G. route census

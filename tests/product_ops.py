@@ -26,6 +26,14 @@ gradients (axpy), and the unfused routes the closing layers take instead of the 
 (conv3_c1_fwd_stats, conv3_c1_wgrad, pw16_fwd / pw16_bwd in a training step, conv3_fwd at the deep levels).  Their references can be
 made wrong on purpose (NEAR_MISS): tests/test_product_ops_cpu.py shows that the same bound on the same inputs then rejects the kernel.
 
+lagn, lagn_pre, lagn_val and pancreasgn are la, la_pre, la_val and pancreas with GroupNorm V-Nets (normalization='groupnorm',
+csrc/gnorm.hip): gnorm_fwd / gnorm_bwd at every level with the step's flags (the statistics rows of the producer the planner names, the
+kernels' own pass at 245 .. 980 blocks per sample, channel scale, the skip add, the table alone, the conv-bias gradient buffer), the fused
+head forward and backward on a GroupNorm table (pw16_fwd_norm, pw16_bwd_norm), and the producers and the dgrad whose rows feed or read such
+a table.  pancreasgn_pre and pancreasgn_val are left out on purpose: they differ from pancreasgn only in N, and the N = 1 and N = 4
+GroupNorm launches are covered by lagn_pre / lagn_val.  Their checks are those of tests/gnorm_seam_checks.py, sample by sample, and their
+references too can be made wrong on purpose (GN_NEAR_MISSES).
+
 The comparator: every element is held to |out - ref64| <= tau * cond, where cond is the same linear op applied in fp64 to |x| and |w| (a
 per-element bound on what rounding can do).  A rel-L2 test spreads an error confined to one tile over the whole tensor; this one does not.
 """
@@ -186,14 +194,15 @@ def k2_wgrad64(x, dy, kind):
 # -------------------------------------------------------------------------------------------------- the steps' keys
 
 
-VAL_CASES = {"la_val": (112, 112, 96), "pancreas_val": (96, 96, 112), "acdc_val": (17, 256, 256), "lares_val": (112, 112, 96)}
+VAL_CASES = {"la_val": (112, 112, 96), "pancreas_val": (96, 96, 112), "acdc_val": (17, 256, 256), "lares_val": (112, 112, 96), "lagn_val": (112, 112, 96)}
 
 
 def make_step(workload, dev):
     """one workload's step as bench.py builds it (configs[1] LA batch 4 / 2 labeled, ACDC 24 / 12, pancreas 4 x 96^3; la8: the LA
     driver's default batch 8 / 4 labeled), the pre-training step of the same driver on the labeled half of that batch (*_pre), or one
     validation pass through the function the driver calls (*_val) on a synthetic case of VAL_CASES' extents: one full chunk of patches
-    (slices) and a remainder chunk of one.  lares, lares_pre, lares_val: la, la_pre, la_val with residual V-Nets (has_residual=True)"""
+    (slices) and a remainder chunk of one.  lares, lares_pre, lares_val: la, la_pre, la_val with residual V-Nets (has_residual=True);
+    lagn, lagn_pre, lagn_val, pancreasgn: la, la_pre, la_val, pancreas with GroupNorm V-Nets (normalization='groupnorm')"""
     from bcp_amd import synth, train_step
     seed = 1337
     np.random.seed(seed)
@@ -201,11 +210,12 @@ def make_step(workload, dev):
     if workload == "la8":
         base, phase = "la", "8"
     ema_model = None
-    if base in ("la", "lares"):
+    if base in ("la", "lares", "lagn"):
         from bcp_amd.networks.net_factory import net_factory
         torch.manual_seed(seed)
-        model = net_factory(net_type="VNet", in_chns=1, class_num=2, mode="train", has_residual=base == "lares")
-        ema_model = net_factory(net_type="VNet", in_chns=1, class_num=2, mode="train", has_residual=base == "lares")
+        kw = dict(has_residual=base == "lares", normalization="groupnorm" if base == "lagn" else "batchnorm")
+        model = net_factory(net_type="VNet", in_chns=1, class_num=2, mode="train", **kw)
+        ema_model = net_factory(net_type="VNet", in_chns=1, class_num=2, mode="train", **kw)
         for p in ema_model.parameters():
             p.detach_()
         ema_model.load_state_dict(model.state_dict())
@@ -251,11 +261,12 @@ def make_step(workload, dev):
             else:
                 def step():
                     return train_step.acdc_self_train_step(model, ema_model, opt, vol, lab, 12)
-    elif base == "pancreas":
+    elif base in ("pancreas", "pancreasgn"):
         from bcp_amd.pancreas import train_pancreas as TP
         from bcp_amd.pancreas.Vnet import create_Vnet
         torch.manual_seed(seed)
-        model, ema_model = create_Vnet(), create_Vnet(ema=True)
+        norm = "groupnorm" if base == "pancreasgn" else "instancenorm"
+        model, ema_model = create_Vnet(normalization=norm), create_Vnet(ema=True, normalization=norm)
         ema_model.load_state_dict(model.state_dict())
         opt = train_step.FlatAdam(model, lr=1e-3)
         if phase == "val":
@@ -1234,6 +1245,248 @@ STEP_KEYS = {
         ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 0),
         ('up_fwd', ((4, 56, 56, 40, 32), (4096,), (16,)), (16,), 0),
     ),
+    "lagn": (
+        ('conv3_c1_fwd_stats', ((2, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 2), 0),
+        ('conv3_c1_wgrad', ((2, 112, 112, 80, 1), (2, 112, 112, 80, 16), (16, 1, 3, 3, 3)), (3,), 1),
+        ('conv3_dgrad_bwdstats', ((2, 28, 28, 20, 64), (397344,), (2, 28, 28, 20, 64)), (64, 3, 1), 1),
+        ('conv3_dgrad_bwdstats', ((2, 56, 56, 40, 32), (99360,), (2, 56, 56, 40, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((2, 7, 7, 5, 256), (6357024,)), (256, 3), 1),
+        ('conv3_fwd', ((2, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((2, 14, 14, 10, 128), (1589280,)), (128, 3), 1),
+        ('conv3_fwd', ((2, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((2, 112, 112, 80, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd_stats', ((2, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 2), 1),
+        ('conv3_fwd_stats', ((2, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 2), 1),
+        ('conv3_fwd_stats', ((2, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 2), 1),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_wgrad', ((2, 7, 7, 5, 256), (2, 7, 7, 5, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 14, 14, 10, 128), (2, 14, 14, 10, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 28, 28, 20, 64), (2, 28, 28, 20, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 56, 56, 40, 32), (2, 56, 56, 40, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 112, 112, 80, 16), (2, 112, 112, 80, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((2, 7, 7, 5, 256), (262144,)), (128,), 1),
+        ('down_dgrad', ((2, 14, 14, 10, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((2, 28, 28, 20, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((2, 56, 56, 40, 32), (4096,)), (16,), 1),
+        ('down_fwd', ((2, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((2, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((2, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((2, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('ema', ((9457332,), (9457332,)), (), 0),
+        ('gnorm_bwd', ((2, 7, 7, 5, 256), (2, 7, 7, 5, 256), (5, 2, 256)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 14, 14, 10, 128), (2, 14, 14, 10, 128), (5, 2, 128)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 28, 28, 20, 64), (2, 28, 28, 20, 64), (5, 2, 64)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 56, 56, 40, 32), (2, 56, 56, 40, 32), (5, 2, 32)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 112, 112, 80, 16), (2, 112, 112, 80, 16), (5, 2, 16)), (1, 1), 0),
+        ('gnorm_fwd', ((2, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('gnorm_fwd', ((2, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('gnorm_fwd', ((2, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('gnorm_fwd', ((2, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('gnorm_fwd', ((2, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('k2_fwd_stats', ((2, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 2), 1),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_wgrad', ((2, 7, 7, 5, 256), (2, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 112, 112, 80, 16), (2, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0),
+        ('mixloss_pair_bwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('mixloss_pair_fwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('plabel_cc_largest', ((2, 112, 112, 80, 2),), (3,), 0),
+        ('pw16_bwd_norm', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1), 0),
+        ('pw16_fwd_norm', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1, 2), 0),
+        ('sgd', ((9448868,), (9448868,), (9448868,)), (), 0),
+        ('up_dgrad', ((2, 14, 14, 10, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((2, 28, 28, 20, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((2, 56, 56, 40, 32), (16384,)), (64,), 1),
+        ('up_dgrad', ((2, 112, 112, 80, 16), (4096,)), (32,), 1),
+        ('up_fwd', ((2, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((2, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((2, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+    ),
+    "lagn_pre": (
+        ('conv3_c1_fwd_stats', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1), 0),
+        ('conv3_c1_wgrad', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 16), (16, 1, 3, 3, 3)), (3,), 1),
+        ('conv3_dgrad_bwdstats', ((1, 56, 56, 40, 32), (99360,), (1, 56, 56, 40, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 14, 14, 10, 128), (1589280,)), (128, 3), 1),
+        ('conv3_fwd', ((1, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((1, 28, 28, 20, 64), (397344,)), (64, 3), 1),
+        ('conv3_fwd', ((1, 112, 112, 80, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd_stats', ((1, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 1), 1),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_wgrad', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((1, 7, 7, 5, 256), (262144,)), (128,), 1),
+        ('down_dgrad', ((1, 14, 14, 10, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((1, 28, 28, 20, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((1, 56, 56, 40, 32), (4096,)), (16,), 1),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('gnorm_bwd', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (5, 1, 256)), (1, 1), 0),
+        ('gnorm_bwd', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (5, 1, 128)), (1, 1), 0),
+        ('gnorm_bwd', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (5, 1, 64)), (1, 1), 0),
+        ('gnorm_bwd', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (5, 1, 32)), (1, 1), 0),
+        ('gnorm_bwd', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (5, 1, 16)), (1, 1), 0),
+        ('gnorm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('gnorm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('gnorm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('gnorm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('gnorm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_wgrad', ((1, 7, 7, 5, 256), (1, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((1, 112, 112, 80, 16), (1, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0),
+        ('mixloss_bwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('mixloss_fwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0),
+        ('pw16_bwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1), 0),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1, 2), 0),
+        ('sgd', ((9448868,), (9448868,), (9448868,)), (), 0),
+        ('up_dgrad', ((1, 14, 14, 10, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((1, 28, 28, 20, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((1, 56, 56, 40, 32), (16384,)), (64,), 1),
+        ('up_dgrad', ((1, 112, 112, 80, 16), (4096,)), (32,), 1),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1),
+    ),
+    "lagn_val": (
+        ('conv3_c1_fwd_stats', ((1, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 1), 0),
+        ('conv3_c1_fwd_stats', ((4, 112, 112, 80, 1), (16, 1, 3, 3, 3), (16,)), (3, 4), 0),
+        ('conv3_fwd', ((1, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((1, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((4, 7, 7, 5, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((4, 14, 14, 10, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd_stats', ((1, 7, 7, 5, 256), (6357024,), (256,)), (256, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 14, 14, 10, 128), (1589280,), (128,)), (128, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 1), 1),
+        ('conv3_fwd_stats', ((1, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 1), 1),
+        ('conv3_fwd_stats', ((4, 7, 7, 5, 256), (6357024,), (256,)), (256, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 14, 14, 10, 128), (1589280,), (128,)), (128, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 28, 28, 20, 64), (397344,), (64,)), (64, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 56, 56, 40, 32), (99360,), (32,)), (32, 3, 4), 1),
+        ('conv3_fwd_stats', ((4, 112, 112, 80, 16), (24864,), (16,)), (16, 3, 4), 1),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 1),
+        ('gnorm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('gnorm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('gnorm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('gnorm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('gnorm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('gnorm_fwd', ((4, 7, 7, 5, 256), (256,), (256,)), (1,), 0),
+        ('gnorm_fwd', ((4, 14, 14, 10, 128), (128,), (128,)), (1,), 0),
+        ('gnorm_fwd', ((4, 28, 28, 20, 64), (64,), (64,)), (1,), 0),
+        ('gnorm_fwd', ((4, 56, 56, 40, 32), (32,), (32,)), (1,), 0),
+        ('gnorm_fwd', ((4, 112, 112, 80, 16), (16,), (16,)), (1,), 0),
+        ('k2_fwd_stats', ((4, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 4), 1),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('overlap_counts', ((112, 112, 96), (112, 112, 96)), (0,), 0),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (2, 16, 1, 1, 1)), (1, 1, 2), 0),
+        ('pw16_fwd_norm', ((4, 112, 112, 80, 16), (5, 4, 16), (2, 16, 1, 1, 1)), (4, 1, 2), 0),
+        ('sw_accumulate', ((112, 112, 80, 2), (112, 112, 96), (112, 112, 96)), (), 0),
+        ('sw_finish', ((112, 112, 96), (112, 112, 96)), (), 0),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 1),
+    ),
+    "pancreasgn": (
+        ('adam', ((9448868,), (9448868,), (9448868,)), (3,), 0),
+        ('conv3_c1_fwd_stats', ((2, 96, 96, 96, 1), (16, 1, 3, 3, 3), (16,)), (3, 2), 0),
+        ('conv3_c1_wgrad', ((2, 96, 96, 96, 1), (2, 96, 96, 96, 16), (16, 1, 3, 3, 3)), (3,), 1),
+        ('conv3_dgrad_bwdstats', ((2, 24, 24, 24, 64), (397344,), (2, 24, 24, 24, 64)), (64, 3, 1), 1),
+        ('conv3_dgrad_bwdstats', ((2, 48, 48, 48, 32), (99360,), (2, 48, 48, 48, 32)), (32, 3, 1), 1),
+        ('conv3_fwd', ((2, 6, 6, 6, 256), (6357024,)), (256, 3), 1),
+        ('conv3_fwd', ((2, 6, 6, 6, 256), (6357024,), (256,)), (256, 3), 1),
+        ('conv3_fwd', ((2, 12, 12, 12, 128), (1589280,)), (128, 3), 1),
+        ('conv3_fwd', ((2, 12, 12, 12, 128), (1589280,), (128,)), (128, 3), 1),
+        ('conv3_fwd', ((2, 96, 96, 96, 16), (24864,)), (16, 3), 1),
+        ('conv3_fwd_stats', ((2, 24, 24, 24, 64), (397344,), (64,)), (64, 3, 2), 1),
+        ('conv3_fwd_stats', ((2, 48, 48, 48, 32), (99360,), (32,)), (32, 3, 2), 1),
+        ('conv3_fwd_stats', ((2, 96, 96, 96, 16), (24864,), (16,)), (16, 3, 2), 1),
+        ('conv3_pack_many', ((800,),), (20,), 0),
+        ('conv3_pack_many', ((1600,),), (40,), 0),
+        ('conv3_wgrad', ((2, 6, 6, 6, 256), (2, 6, 6, 6, 256), (256, 256, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 12, 12, 12, 128), (2, 12, 12, 12, 128), (128, 128, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 24, 24, 24, 64), (2, 24, 24, 24, 64), (64, 64, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 48, 48, 48, 32), (2, 48, 48, 48, 32), (32, 32, 3, 3, 3)), (3,), 2),
+        ('conv3_wgrad', ((2, 96, 96, 96, 16), (2, 96, 96, 96, 16), (16, 16, 3, 3, 3)), (3,), 2),
+        ('down_dgrad', ((2, 6, 6, 6, 256), (262144,)), (128,), 1),
+        ('down_dgrad', ((2, 12, 12, 12, 128), (65536,)), (64,), 1),
+        ('down_dgrad', ((2, 24, 24, 24, 64), (16384,)), (32,), 1),
+        ('down_dgrad', ((2, 48, 48, 48, 32), (4096,)), (16,), 1),
+        ('down_fwd', ((2, 12, 12, 12, 128), (262144,), (256,)), (256,), 1),
+        ('down_fwd', ((2, 24, 24, 24, 64), (65536,), (128,)), (128,), 1),
+        ('down_fwd', ((2, 48, 48, 48, 32), (16384,), (64,)), (64,), 1),
+        ('down_fwd', ((2, 96, 96, 96, 16), (4096,), (32,)), (32,), 1),
+        ('ema', ((9448868,), (9448868,)), (), 0),
+        ('gnorm_bwd', ((2, 6, 6, 6, 256), (2, 6, 6, 6, 256), (5, 2, 256)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 12, 12, 12, 128), (2, 12, 12, 12, 128), (5, 2, 128)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 24, 24, 24, 64), (2, 24, 24, 24, 64), (5, 2, 64)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 48, 48, 48, 32), (2, 48, 48, 48, 32), (5, 2, 32)), (1, 1), 0),
+        ('gnorm_bwd', ((2, 96, 96, 96, 16), (2, 96, 96, 96, 16), (5, 2, 16)), (1, 1), 0),
+        ('gnorm_fwd', ((2, 6, 6, 6, 256), (256,), (256,)), (1,), 0),
+        ('gnorm_fwd', ((2, 12, 12, 12, 128), (128,), (128,)), (1,), 0),
+        ('gnorm_fwd', ((2, 24, 24, 24, 64), (64,), (64,)), (1,), 0),
+        ('gnorm_fwd', ((2, 48, 48, 48, 32), (32,), (32,)), (1,), 0),
+        ('gnorm_fwd', ((2, 96, 96, 96, 16), (16,), (16,)), (1,), 0),
+        ('k2_fwd_stats', ((2, 48, 48, 48, 32), (4096,), (16,)), (1, 16, 2), 1),
+        ('k2_pack_many', ((512,),), (8,), 0),
+        ('k2_pack_many', ((1024,),), (16,), 0),
+        ('k2_wgrad', ((2, 6, 6, 6, 256), (2, 12, 12, 12, 128), (256, 128, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 6, 6, 6, 256), (256, 128, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 24, 24, 24, 64), (128, 64, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 12, 12, 12, 128), (128, 64, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 48, 48, 48, 32), (64, 32, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 24, 24, 24, 64), (64, 32, 2, 2, 2)), (0,), 2),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 96, 96, 96, 16), (32, 16, 2, 2, 2)), (1,), 2),
+        ('k2_wgrad', ((2, 96, 96, 96, 16), (2, 48, 48, 48, 32), (32, 16, 2, 2, 2)), (0,), 2),
+        ('mix_box', ((1, 96, 96, 96, 1), (1, 96, 96, 96, 1)), (), 0),
+        ('mixloss_pair_bwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0),
+        ('mixloss_pair_fwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0),
+        ('plabel_cc_largest', ((2, 96, 96, 96, 2),), (2,), 0),
+        ('pw16_bwd_norm', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 96, 96, 96, 2)), (2, 1), 0),
+        ('pw16_fwd_norm', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 16, 1, 1, 1)), (2, 1, 2), 0),
+        ('up_dgrad', ((2, 12, 12, 12, 128), (262144,)), (256,), 1),
+        ('up_dgrad', ((2, 24, 24, 24, 64), (65536,)), (128,), 1),
+        ('up_dgrad', ((2, 48, 48, 48, 32), (16384,)), (64,), 1),
+        ('up_dgrad', ((2, 96, 96, 96, 16), (4096,)), (32,), 1),
+        ('up_fwd', ((2, 6, 6, 6, 256), (262144,), (128,)), (128,), 1),
+        ('up_fwd', ((2, 12, 12, 12, 128), (65536,), (64,)), (64,), 1),
+        ('up_fwd', ((2, 24, 24, 24, 64), (16384,), (32,)), (32,), 1),
+    ),
 }
 
 TAU = 2.0 ** -14            # elementwise bound for convolutions, GEMMs and norms: |out - ref64| <= TAU * cond
@@ -1247,19 +1500,32 @@ EPS = 1e-5
 
 
 def network_of(wl):
-    """the workload whose network (and configuration) `wl` runs: la_pre, la_val, la8 -> la; lares_pre, lares_val -> lares (the residual V-Net)"""
+    """the workload whose network (and configuration) `wl` runs: la_pre, la_val, la8 -> la; lares_pre, lares_val -> lares (the residual
+    V-Net); lagn_pre, lagn_val -> lagn (the GroupNorm V-Net, as pancreasgn)"""
     return "la" if wl == "la8" else wl.partition("_")[0]
+
+
+GN_NETWORKS = ("lagn", "pancreasgn")
+# ops whose key can repeat a plain workload's while the table behind or in front of the launch is a GroupNorm table (groups = samples)
+GN_TABLE_OPS = ("conv3_dgrad_bwdstats", "pw16_fwd_norm", "k2_fwd_stats", "conv3_c1_fwd_stats")
+
+
+def is_gn(wl):
+    """whether `wl` runs GroupNorm V-Nets (normalization='groupnorm'): every norm table is per sample, its mean and rstd per group of C / 16
+    adjacent channels"""
+    return network_of(wl) in GN_NETWORKS
 
 
 def stats_fused(wl, key):
     """whether `wl` feeds the norm behind the conv3_fwd_stats launch `key` from its fused partials: STEP_VARIANTS has a 'partial'
     epilogue at the norm key of the conv's output"""
     ys = tuple(key[1][0][:-1]) + (key[2][0],)
-    return any(k[0] in ("norm_fwd", "norm_fwd_res") and tuple(k[1][0]) == ys and any("partial" in f for f in fl) for k, fl in STEP_VARIANTS.get(wl, {}).items())
+    return any(k[0] in ("norm_fwd", "norm_fwd_res", "gnorm_fwd") and tuple(k[1][0]) == ys and any("partial" in f for f in fl) for k, fl in STEP_VARIANTS.get(wl, {}).items())
 
 
 def step_groups(wl):
-    """norm groups of the workload's network calls: 2 in the self-training steps; pre-training calls the network without groups="""
+    """norm groups of the workload's network calls: 2 in the self-training steps; pre-training calls the network without groups=.  (A
+    GroupNorm network ignores them: its statistics groups are the samples, is_gn)"""
     return 1 if wl.endswith(("_pre", "_val")) else STEP_GROUPS
 
 
@@ -1289,12 +1555,14 @@ def _pre_norm(g, shape):
     return (torch.randn(shape, generator=g, dtype=torch.float64) * sc + off).float()
 
 
-def drive_conv(ops, dev, key, g, groups=STEP_GROUPS, fused=True):
+def drive_conv(ops, dev, key, g, groups=STEP_GROUPS, fused=True, gn=False):
     """conv3_fwd / conv3_fwd_stats / conv3_fwd_raw / conv3_dgrad_bwdstats: the output against sum over 27 (9) shifted matmuls in fp64,
     sample by sample (the reference of an N = 4 validation chunk is the cost of its row).  namax == 0 (the validation pass: norm_eval
     leaves no |max| on its output): the operand must reach the library without one and the launch must not take the two-plane fp16 instance.
     fused (conv3_fwd_stats): whether the pass feeds the norm behind from this launch's statistics partials (stats_fused) -- the
-    pancreas validation pass calls conv3_fwd_stats at every level and gets none at the small ones, where the call is a plain conv"""
+    pancreas validation pass calls conv3_fwd_stats at every level and gets none at the small ones, where the call is a plain conv.
+    gn (conv3_dgrad_bwdstats of a GroupNorm workload): the table of the layer in front comes from gnorm_fwd with one group per sample,
+    and the epilogue's backward-statistics rows are held against sums formed with GROUP statistics"""
     from bcp_amd import hip_ops as H
     op, shapes, ints, namax = key
     xs = shapes[0]
@@ -1311,16 +1579,23 @@ def drive_conv(ops, dev, key, g, groups=STEP_GROUPS, fused=True):
         if namax:
             _amax(H, xd, dev)
         yp = _pre_norm(g, shapes[2]).to(dev)
-        act, Gn = ints[2], groups            # (the key's ints are Cin, KD, act: the groups argument comes fourth)
+        act, Gn = ints[2], xs[0] if gn else groups            # (the key's ints are Cin, KD, act: the groups argument comes fourth)
         C = yp.shape[-1]
         gam = (torch.rand(C, generator=g) + 0.5).to(dev)
         bet = (torch.rand(C, generator=g) - 0.5).to(dev)
-        _, st = ops.norm_fwd(yp, Gn, gam, bet, torch.zeros(C, device=dev), torch.ones(C, device=dev), act)
+        if gn:
+            yp = _seam()._pre_norm(_np_rng(g), xs[0], tuple(shapes[2][1:4]), C).to(dev)      # (offsets of order 30, every sample its own)
+            _, st = ops.gnorm_fwd(yp, gam, bet, act)
+        else:
+            _, st = ops.norm_fwd(yp, Gn, gam, bet, torch.zeros(C, device=dev), torch.ones(C, device=dev), act)
         res, part, rows = ops.conv3_dgrad_bwdstats(xd, wd, Cin, KD, yp, st, act, Gn)
         assert rows > 0 or dev.type == "cpu", f"{op} {xs}: no fused backward statistics at the step's shape"
         if rows:
             # the epilogue's (sum dz, sum dz * xhat) partials of the norm layer behind: fp64 sums of the kernel's own da
-            _, z, xh, _, _, fcond = norm_ref64(yp.cpu(), Gn, gam.cpu(), bet.cpu(), act)
+            _, z, xh, _, _, fcond = _seam().gn_ref64(yp.cpu(), gam.cpu(), bet.cpu(), act)[:6] if gn else norm_ref64(yp.cpu(), Gn, gam.cpu(), bet.cpu(), act)
+            if gn and NEAR_MISS == "gn_channel_statistics":      # (test_product_ops_cpu: every channel its own statistics)
+                _, z, xh, _, _, fcond = _seam().gn_ref64(yp.cpu(), gam.cpu(), bet.cpu(), act, how="channel")
+                _near_miss_hit(C > 16)
             dact = _acts(act, z)[1]
             da64 = res.cpu().double()
             dz, xg = (da64 * dact).reshape(Gn, -1, C), xh.reshape(Gn, -1, C)
@@ -1621,7 +1896,7 @@ NEAR_MISSES = ("pattern_from_z", "residual_behind_activation", "neighbour_chan_s
                "dres_without_chan_scale", "c1c2_from_z", "eval_batch_statistics")
 KINK_CAP = 1e-4                 # at most this share of a tensor's elements may be exempt as kink elements (asserted on the reference alone)
 TAU_DRES = 2.0 ** -22           # dres = da * chan_scale * act'(t): two fp32 multiplications, each at most 2^-24 relative
-KINK_SHARES = []                # (tag, share) of every residual backward case run (the report of the largest share seen)
+KINK_SHARES = []                # (tag, share) of every residual / GroupNorm backward case run (the report of the largest share seen)
 
 
 def _near_miss_hit(changed=True):
@@ -1864,7 +2139,7 @@ def drive_axpy(ops, dev, key, g):
     return out
 
 
-def drive_c1_stats(ops, dev, key, g):
+def drive_c1_stats(ops, dev, key, g, gn=False):
     """conv3_c1_fwd_stats, the first layer in front of a closing norm (block_one of the residual V-Net): the fp64 conv sample by sample,
     and the statistics rows of its epilogue against fp64 column sums of the kernel's own output, as drive_conv checks conv3_fwd_stats'"""
     op, shapes, ints, namax = key
@@ -1888,6 +2163,8 @@ def drive_c1_stats(ops, dev, key, g):
         for j, (s_, c) in enumerate(((yg.sum(1), yg.abs().sum(1)), ((yg * yg).sum(1), (yg * yg).sum(1)))):
             r = float(((pt[..., j] - s_).abs() / c.clamp_min(1e-300)).max())
             assert r <= 1e-12, f"{op} {xs}: fused statistics partial {j} off by {r:.3e} x sum|.|"
+        if gn:
+            _gn_table_from_rows(ops, dev, g, f"{op} {xs}", yd, part, rows, G)
     return [(op, worst)]
 
 
@@ -2143,7 +2420,7 @@ TAU_K2_STATS_MEASURED = 1.89e-9
 TAU_K2_STATS = 2 * TAU_K2_STATS_MEASURED
 
 
-def drive_k2(ops, dev, key, g, variants=((),)):
+def drive_k2(ops, dev, key, g, variants=((),), gn=False):
     """down_fwd / down_dgrad / up_fwd / up_dgrad / k2_fwd_stats / k2_wgrad / pw_fwd at the step's row counts, against the strided-view
     fp64 matmuls (down64, up64, k2_wgrad64).  The weights go through ops.k2_pack with the launch's PACK_* kind; the flags of `variants`
     (out given, accumulate) are the step's: down_dgrad adds into the skip gradient, every k2_wgrad into the flat gradient buffer."""
@@ -2234,6 +2511,8 @@ def drive_k2(ops, dev, key, g, variants=((),)):
                     print(f"[product-op] {tag}: fused statistics partial {j} off by {r:.3e} x sum|.| ({rows} rows)")
                     worst = max(worst, r)
                 assert worst <= TAU_K2_STATS, f"{tag}: fused statistics partials off by {worst:.3e} x sum|.| (bound {TAU_K2_STATS:.3e})"
+                if gn:
+                    _gn_table_from_rows(ops, dev, g, tag, res, part, rows, G)
             else:
                 res = plain(xd, bp, bd, Co)
         elif fwd or op == "pw_fwd":
@@ -2382,15 +2661,15 @@ def _step_network(wl, dev, ops):
     net = _NETS.get((wl, dev.type))
     if net is None:
         torch.manual_seed(1337)
-        if wl in ("la", "lares"):
+        if wl in ("la", "lares", "lagn"):
             from bcp_amd.networks.VNet import VNet
-            net = VNet(n_channels=1, n_classes=2, normalization="batchnorm", has_dropout=True, has_residual=wl == "lares")
+            net = VNet(n_channels=1, n_classes=2, normalization="groupnorm" if wl == "lagn" else "batchnorm", has_dropout=True, has_residual=wl == "lares")
         elif wl == "acdc":
             from bcp_amd.networks.unet import UNet_2d
             net = UNet_2d(in_chns=1, class_num=4)
         else:
             from bcp_amd.pancreas.Vnet import VNet
-            net = VNet()
+            net = VNet(normalization="groupnorm" if wl == "pancreasgn" else "instancenorm")
         net = _NETS[(wl, dev.type)] = net.to(dev).flatten_()
     return net.set_ops(ops)
 
@@ -2985,6 +3264,309 @@ def drive_mixloss_single(ops, dev, key, g, variants=((),)):
     return out
 
 
+# -------------------------------------------------------------------------------------------------- the GroupNorm V-Nets
+# lagn, lagn_pre, lagn_val, pancreasgn: normalization='groupnorm' (csrc/gnorm.hip).  The checks are those of tests/gnorm_seam_checks.py
+# (gn_ref64, BwdRef, _table_check, dbias_closed64: the bound TAU * cond with the 2^-18 kink allowance, KINK_CAP on the reference before the
+# device result is read, TAU_BIAS_CLOSED where the partial rows are visible), walked sample by sample -- a group never leaves its sample,
+# so the reference of a 32 M element row is two of 16 M.  Inputs are the seam file's: per-channel offsets of order 30, per-sample offsets
+# and scales that all differ.  Where the step feeds a layer's statistics from a producer's epilogue ('partial'), the driver asks the
+# network's own planner which producers those are at the in-step shape (gn_routes) and launches each of them.
+GN_PASSES = {"lagn": ("la", (112, 112, 80), ((2, "teacher"), (2, "student"))), "lagn_pre": ("la", (112, 112, 80), ((1, "student"),)),
+             "lagn_val": ("la", (112, 112, 80), ((4, "eval"), (1, "eval"))), "pancreasgn": ("pancreas", (96, 96, 96), ((2, "teacher"), (2, "student")))}
+GN_NEAR_MISSES = ("gn_channel_statistics", "gn_shifted_table", "gn_block_dropped", "gn_row4_flipped")
+_GN_NETS = {}
+
+
+def _seam():
+    import gnorm_seam_checks as S        # (imports this module: not at load time)
+    return S
+
+
+def gn_routes(ops, wl, ys):
+    """the planner (VNet.plan_forward: shape queries, no launch) for the passes of the GroupNorm workload `wl` -> {(producer, cin, flags)}
+    of the layers whose gnorm_fwd reads a tensor of the in-step shape ys; producer: 'c1' / 'c3' / 'up' / 'down' (the seam file's names),
+    flags: the epilogue as STEP_VARIANTS spells it ('partial' where the producer's row query answers > 0)"""
+    from bcp_amd.networks.VNet import VNet
+    variant, sp, passes = GN_PASSES[wl]
+    net = _GN_NETS.get((variant, id(ops)))
+    if net is None:
+        net = _GN_NETS[(variant, id(ops))] = VNet(n_channels=1, n_classes=2, normalization="groupnorm", has_dropout=variant == "la", variant=variant).set_ops(ops)
+    found = set()
+    for N, mode in passes:
+        train = mode != "eval"
+        plan = net.plan_forward(N, *sp, 2, save=mode == "student", training=train, dropout=net.has_dropout and train)
+        for L, r in zip(net._layers, plan.layers):
+            if tuple(r.yshape) == tuple(ys) and r.norm == "gnorm_fwd":
+                flags = tuple(f for f, on in (("chan_scale", r.dropout), ("partial", r.rows > 0), ("residual", L.skip_pop), ("stats_only", r.stats_only)) if on)
+                found.add(({"c1": "c1", "c3": "c3", "dw": "down", "up": "up"}[L.kind], L.cin, flags))
+    return found
+
+
+def _np_rng(g):
+    return np.random.default_rng(int(torch.randint(1, 1 << 31, (1,), generator=g)))
+
+
+def _gn_producer(ops, dev, rng, prod, Cin, ys, tag):
+    """the launch of the step's kind that leaves y of shape ys WITH its statistics rows (the seam file's _produce, the *_fwd_stats launch
+    alone) -> (y on the device, partial, rows); rows == 0 where the reduced simulator shape is not served: the caller's own pass then"""
+    S = _seam()
+    N, C = ys[0], ys[-1]
+    sp = tuple(ys[1:4])
+    if prod == "up":
+        if any(e % 2 for e in sp):
+            return None, None, 0
+        sp = tuple(e // 2 for e in sp)
+    elif prod == "down":
+        sp = tuple(2 * e for e in sp)
+    if S.fwd_rows(ops, prod, (N,) + sp + (Cin,), C, N) <= 0:
+        assert dev.type == "cpu", f"{tag}: the producer '{prod}' leaves no statistics rows at the step's shape"
+        return None, None, 0
+    return S._produce(ops, dev, rng, prod, N, Cin, C, sp, tag, verify=False)
+
+
+def _gn_how(S, y, n, C):
+    """the reference of sample n: GroupNorm's, or -- NEAR_MISS -- one that is wrong the way a plausible kernel would be: every channel its
+    own statistics, sample n - 1's table, one block of the statistics pass left out -> (how, stats) for gn_ref64 / BwdRef"""
+    N = y.shape[0]
+    if NEAR_MISS == "gn_channel_statistics":
+        _near_miss_hit(C > 16)
+        return "channel", None
+    if NEAR_MISS == "gn_shifted_table":
+        _near_miss_hit(N > 1)
+        return "group", S._stats64(y[(n - 1) % N:(n - 1) % N + 1].double().reshape(1, -1, C))
+    if NEAR_MISS == "gn_block_dropped":
+        rows = y[n].numel() // C
+        chunk = -(-rows // max(2, S.own_geometry(rows, C)[0]))
+        _near_miss_hit(chunk < rows)
+        return ("drop", 0, chunk), None
+    return "group", None
+
+
+def _gn_mult(cs, n, shape):
+    return None if cs is None else cs[n:n + 1].double().view(1, *([1] * (len(shape) - 2)), shape[-1])
+
+
+def _worse(a, b):
+    return b if a is None or b[0] > a[0] else a
+
+
+def drive_gnorm_fwd(ops, dev, key, g, variants=((),), wl="lagn", table_key=None):
+    """gnorm_fwd with each epilogue the step uses at this key: the statistics rows of every producer the planner names for it (or the
+    kernel's own pass: hundreds of blocks per sample at these shapes), channel scale, the decoder's skip add, the table alone in front
+    of the fused head.  The five table rows, a elementwise, the published |max|"""
+    from bcp_amd import hip_ops as H
+    S = _seam()
+    op, shapes, ints, namax = key
+    ys, act = tuple(shapes[0]), ints[0]
+    N, C = ys[0], ys[-1]
+    routes = gn_routes(ops, wl, tuple((table_key or key)[1][0]))
+    out = []
+    for flags in variants:
+        srcs = [None]
+        if "partial" in flags:
+            srcs = sorted({(p, cin) for p, cin, f in routes if f == tuple(flags)})
+            assert srcs, f"{op} {ys} {flags}: the planner names no producer for this epilogue"
+        else:
+            assert any(f == tuple(flags) for _, _, f in routes) or "stats_only" in flags, f"{op} {ys} {flags}: not an epilogue the planner emits here"
+        for src in srcs:
+            rng = _np_rng(g)
+            tag = f"{op} {ys} [{'+'.join(flags) or 'plain'}{'' if src is None else f' {src[0]} {src[1]}->{C}'}]"
+            name = op + ("" if not flags else " " + "+".join(flags)) + ("" if src is None else " " + src[0])
+            yd, part, rows = _gn_producer(ops, dev, rng, src[0], src[1], ys, tag) if src else (None, None, 0)
+            if yd is None:
+                yd = S._pre_norm(rng, N, ys[1:4], C).to(dev)
+            y = yd.cpu()
+            gamma, beta = S._affine(rng, C)
+            cs = S._chan_scale(rng, N, C) if "chan_scale" in flags else None
+            res = torch.from_numpy(rng.standard_normal(ys, dtype=np.float32)) if "residual" in flags else None
+            kw = dict(partial=part, nb=rows) if rows else {}
+            a, st = ops.gnorm_fwd(yd, gamma.to(dev), beta.to(dev), act, chan_scale=None if cs is None else cs.to(dev),
+                                  residual=None if res is None else res.to(dev), stats_only="stats_only" in flags, **kw)
+            stc = st.cpu()
+            worst = (0.0, "table") if a is None else None
+            for n in range(N):
+                sl = slice(n, n + 1)
+                if NEAR_MISS is None:
+                    S._table_check(f"{tag} sample {n}", stc[:, sl], y[sl], gamma, beta)
+                if a is None:
+                    continue
+                how, stats = _gn_how(S, y, n, C)
+                ar, _, _, _, _, cond = S.gn_ref64(y[sl], gamma, beta, act, how=how, stats=stats)
+                mult = _gn_mult(cs, n, ys)
+                if mult is not None:
+                    ar, cond = ar * mult, cond * mult.abs()
+                if res is not None:
+                    ar, cond = ar + res[sl].double(), cond + res[sl].double().abs()
+                worst = _worse(worst, check_elementwise(a[sl].cpu(), ar, cond, TAU, f"{tag} sample {n}"))
+            if a is not None:
+                assert H.amax_value(a._bcp_amax) == float(a.abs().max()), f"{tag}: |max| of a"
+            out.append((name, worst))
+    return out
+
+
+def drive_gnorm_bwd(ops, dev, key, g, variants=((),), wl="lagn", table_key=None):
+    """gnorm_bwd with each flag set the step uses at this key: the backward statistics from a real conv3_dgrad_bwdstats launch's rows
+    ('partial') or from the kernel's own pass, channel scale, accumulation onto non-zero gradients, with and without the conv-bias gradient
+    buffer.  dy elementwise, dgamma / dbeta, the conv-bias gradient (bias_chain; bias_closed from the producer's rows), the |max|"""
+    from bcp_amd import hip_ops as H
+    import kernel_checks as K
+    S = _seam()
+    op, shapes, ints, namax = key
+    ys, act, accumulate = tuple(shapes[0]), ints[0], bool(ints[1])
+    N, C = ys[0], ys[-1]
+    sp, cg = ys[1:4], C // S.GROUPS
+    out = []
+    for flags in variants:
+        assert ("accumulate" in flags) == accumulate, (key, flags)
+        rng = _np_rng(g)
+        tag = f"{op} {ys} [{'+'.join(flags) or 'plain'}]"
+        y = S._pre_norm(rng, N, sp, C)
+        gamma, beta = S._affine(rng, C)
+        yd, gd = y.to(dev), gamma.to(dev)
+        _, st = ops.gnorm_fwd(yd, gd, beta.to(dev), act)
+        cs = S._chan_scale(rng, N, C) if "chan_scale" in flags else None
+        part, rows = None, 0
+        if "partial" in flags:
+            rows = S.bwd_rows(ops, "c3", ys, C, N)
+            assert rows > 0 or dev.type == "cpu", f"{tag}: conv3_dgrad_bwdstats leaves no rows at the step's shape"
+        if rows:
+            _, wd = ops.conv3_pack((K.R(rng, C, C, 3, 3, 3) * 0.1).to(dev).contiguous(), 3)
+            dad, part, nb = ops.conv3_dgrad_bwdstats(_amax(H, K.to_cl(K.R(rng, N, C, *sp)).contiguous().to(dev), dev), wd, C, 3, yd, st, act, N)
+            assert nb == rows, (tag, nb, rows)
+            da = dad.cpu()
+        else:
+            da = (K.to_cl(K.R(rng, N, C, *sp)) + 5.0).contiguous()
+            dad = da.to(dev)
+        g0, gr = S._grad_start(rng, C, accumulate, dev)
+        if "dbias" not in flags:
+            gr[2] = None
+        dy = ops.gnorm_bwd(yd, dad, st, gd, act, gr[0], gr[1], gr[2], accumulate, chan_scale=None if cs is None else cs.to(dev),
+                           **(dict(partial=part, nb=rows) if rows else {}))
+        worst = None
+        acc = [torch.zeros(C, dtype=torch.float64) for _ in range(9)]      # sums, conds and kink allowances of dbeta, dgamma, dbias
+        rstd, devs, closed = [], [], torch.zeros(C, dtype=torch.float64)
+        refs = [S.BwdRef(y[n:n + 1], gamma, beta, act, da[n:n + 1].double(), _gn_mult(cs, n, ys), how=how, stats=stats)
+                for n, (how, stats) in ((n, _gn_how(S, y, n, C)) for n in range(N))]
+        S._kink_cap(tag, torch.cat([r_.kink for r_ in refs]))               # (on the reference, before the device result is read)
+        KINK_SHARES.append((tag, sum(float(r_.kink.sum()) for r_ in refs) / y.numel()))
+        print(f"[product-op] {tag}: {KINK_SHARES[-1][1]:.2e} of the elements at the activation's kink (cap {S.KINK_CAP:.0e})")
+        for n in range(N):
+            sl = slice(n, n + 1)
+            ref, refs[n] = refs[n], None
+            r = S._ratio(dy[sl], ref.dy, ref.cond, ref.allow)
+            assert r <= TAU, f"{tag} sample {n}: dy off by {r:.3e} x cond (bound {TAU:.3e})"
+            worst = _worse(worst, (r / TAU, f"sample {n}"))
+            xa = ref.xg.abs()
+            for i, t in enumerate((ref.dz.sum((0, 1)), ref.dz.abs().sum((0, 1)), ref.dk.sum((0, 1)),
+                                   (ref.dz * ref.xg).sum((0, 1)), (ref.dz.abs() * xa).sum((0, 1)), (ref.dk * xa).sum((0, 1)),
+                                   ref.dbias, ref.dbias_cond, ref.dbias_allow)):
+                acc[i] += t
+            if NEAR_MISS == "gn_row4_flipped":
+                closed += S.dbias_closed64(ref.dz.sum(1), (ref.dz * ref.xg).sum(1), ref.gm, ref.rstd, ref.dev, ref.rows, flip=True)[0]
+            rstd.append(ref.rstd)
+            devs.append(ref.dev)
+            del ref
+        assert H.amax_value(dy._bcp_amax) == float(dy.abs().max()), f"{tag}: |max| of dy"
+        for nm, t, base, i in (("dbeta", gr[1], g0[1], 0), ("dgamma", gr[0], g0[0], 3)):
+            r = S._ratio(t, base.double() + acc[i], base.double().abs() + acc[i + 1], acc[i + 2])
+            assert r <= TAU, f"{tag}: {nm} off by {r:.3e} x cond"
+        if gr[2] is not None:
+            assert cg > 1, key
+            bias = acc[6]
+            if NEAR_MISS == "gn_row4_flipped":
+                bias = closed
+                _near_miss_hit(True)
+            rb = S._ratio(gr[2], g0[2].double() + bias, g0[2].double().abs() + acc[7], acc[8])
+            assert rb <= TAU, f"{tag}: conv-bias gradient off by {rb:.3e} x cond (bias_chain, bound {TAU:.3e})"
+            if rows and NEAR_MISS is None:      # bias_closed: the closed form in fp64 from the very rows the finalize read
+                ps = _partials(part, N, rows, C)
+                val, cc = S.dbias_closed64(ps[..., 0], ps[..., 1], gamma.double(), torch.cat(rstd), torch.cat(devs), y[0].numel() // C)
+                rc = S._ratio(gr[2], g0[2].double() + val, g0[2].double().abs() + cc)
+                assert rc <= S.TAU_BIAS_CLOSED, f"{tag}: conv-bias gradient off by {rc:.3e} x cond_c from the producer's own rows (bound 2^-22)"
+        out.append((op + ("" if not flags else " " + "+".join(flags)), worst))
+    return out
+
+
+def drive_gn_head(ops, dev, key, g, variants=((),), wl="lagn", table_key=None):
+    """the fused 16 -> C head on a GroupNorm table.  pw16_fwd_norm: logits from the raw conv output and the table gnorm_fwd(stats_only)
+    makes from a real conv3_fwd_stats launch's rows, as the network runs it (groups = N).  pw16_bwd_norm: the gradient w.r.t. the
+    activation elementwise, the head's weight and bias gradients as bounded sums, accumulated where the step accumulates"""
+    import kernel_checks as K
+    S = _seam()
+    op, shapes, ints, namax = key
+    ys = tuple(shapes[0])
+    G, act = ints[0], ints[1]
+    N, C, Cout = ys[0], ys[-1], 2
+    assert G == N and C == 16, key
+    fwd = op == "pw16_fwd_norm"
+    out = []
+    for flags in variants:
+        rng = _np_rng(g)
+        tag = f"{op} {ys} [{'+'.join(flags) or 'plain'}]"
+        name = op + ("" if not flags else " " + "+".join(flags))
+        yd, part, rows = _gn_producer(ops, dev, rng, "c3", C, ys, tag)
+        if yd is None:
+            yd = S._pre_norm(rng, N, ys[1:4], C).to(dev)
+        y = yd.cpu()
+        gamma, beta = S._affine(rng, C)
+        cs = S._chan_scale(rng, N, C) if "chan_scale" in flags else None
+        csd = None if cs is None else cs.to(dev)
+        none, st = ops.gnorm_fwd(yd, gamma.to(dev), beta.to(dev), act, chan_scale=csd, stats_only=True, **(dict(partial=part, nb=rows) if rows else {}))
+        assert none is None
+        w = (K.R(rng, Cout, C, 1, 1, 1) * (2.0 / C) ** 0.5).contiguous()
+        b = K.R(rng, Cout) * 0.1
+        W = w.double().reshape(Cout, C)
+        acc = "accumulate" in flags
+        if fwd:
+            res = ops.pw16_fwd_norm(yd, st, csd, G, act, w.to(dev), b.to(dev), Cout)
+        else:
+            dl = K.to_cl(K.R(rng, N, Cout, *ys[1:4])).contiguous()
+            dw0, db0 = (K.R(rng, Cout, C, 1, 1, 1) * 0.5 + 1.0, K.R(rng, Cout) * 0.5 - 1.0) if acc else (torch.zeros(Cout, C, 1, 1, 1), torch.zeros(Cout))
+            dwd, dbd = ((dw0.clone().contiguous().to(dev), db0.clone().to(dev)) if acc
+                        else (torch.full((Cout, C, 1, 1, 1), float("nan"), device=dev), torch.full((Cout,), float("nan"), device=dev)))
+            res = ops.pw16_bwd_norm(yd, st, csd, G, act, dl.to(dev), w.to(dev), dwd, dbd, accumulate=acc)
+            dwr, dwc = dw0.double().reshape(Cout, C).clone(), dw0.double().abs().reshape(Cout, C).clone()
+            dbr, dbc = db0.double().clone(), db0.double().abs().clone()
+        stc = st.cpu()
+        worst = None
+        for n in range(N):
+            sl = slice(n, n + 1)
+            if NEAR_MISS is None:
+                S._table_check(f"{tag} sample {n}", stc[:, sl], y[sl], gamma, beta)
+            how, stats = _gn_how(S, y, n, C)
+            ar, _, _, _, _, cond = S.gn_ref64(y[sl], gamma, beta, act, how=how, stats=stats)
+            mult = _gn_mult(cs, n, ys)
+            if mult is not None:
+                ar, cond = ar * mult, cond * mult.abs()
+            if fwd:
+                worst = _worse(worst, check_elementwise(res[sl].cpu(), ar @ W.t() + b.double(), cond @ W.abs().t() + b.double().abs(), TAU, f"{tag} sample {n}"))
+                continue
+            d2 = dl[sl].double().reshape(-1, Cout)
+            dwr += d2.t() @ ar.reshape(-1, C)
+            dwc += d2.abs().t() @ cond.reshape(-1, C)
+            dbr += d2.sum(0)
+            dbc += d2.abs().sum(0)
+            worst = _worse(worst, check_elementwise(res[sl].cpu(), dl[sl].double() @ W, dl[sl].double().abs() @ W.abs(), TAU, f"{tag} dh sample {n}"))
+        out.append((name, worst))
+        if not fwd:
+            out.append((name + " dw", check_elementwise(dwd.cpu().reshape(Cout, C), dwr, dwc, TAU, tag + " dw")))
+            out.append((name + " db", check_elementwise(dbd.cpu(), dbr, dbc, TAU, tag + " db")))
+    return out
+
+
+def _gn_table_from_rows(ops, dev, g, tag, yd, part, rows, G):
+    """a producer row of a GroupNorm workload: the table gnorm_fwd (groups = N) makes from the launch's statistics rows, sample by sample"""
+    S = _seam()
+    N, C = yd.shape[0], yd.shape[-1]
+    assert G == N, f"{tag}: a GroupNorm network asks for one statistics group per sample, the key says {G} for {N}"
+    gamma, beta = S._affine(_np_rng(g), C)
+    none, st = ops.gnorm_fwd(yd, gamma.to(dev), beta.to(dev), 1, partial=part, nb=rows, stats_only=True)
+    assert none is None
+    y, stc = yd.cpu(), st.cpu()
+    for n in range(N):
+        S._table_check(f"{tag}: gnorm_fwd from the launch's rows, sample {n}", stc[:, n:n + 1], y[n:n + 1], gamma, beta)
+
+
 DRIVERS = {"conv3_fwd": drive_conv, "conv3_fwd_stats": drive_conv, "conv3_fwd_raw": drive_conv, "conv3_dgrad_bwdstats": drive_conv,
            "conv3_wgrad": drive_wgrad, "norm_fwd": drive_norm_fwd, "norm_bwd": drive_norm_bwd,
            "sgd": drive_optim, "ema": drive_optim, "adam": drive_optim,
@@ -2999,7 +3581,8 @@ DRIVERS = {"conv3_fwd": drive_conv, "conv3_fwd_stats": drive_conv, "conv3_fwd_ra
            "conv3_c1_fwd": drive_c1_plain, "pw16_fwd": drive_pw16, "copy_channels": drive_copy_channels,
            "sw_accumulate": drive_sw, "sw_finish": drive_sw, "overlap_counts": drive_overlap, "plabel_argmax4": drive_argmax4,
            "norm_fwd_res": drive_norm_fwd_res, "norm_bwd_res": drive_norm_bwd_res, "norm_eval_res": drive_norm_eval_res, "axpy": drive_axpy,
-           "conv3_c1_fwd_stats": drive_c1_stats, "conv3_c1_wgrad": drive_c1_wgrad, "pw16_bwd": drive_pw16_bwd}
+           "conv3_c1_fwd_stats": drive_c1_stats, "conv3_c1_wgrad": drive_c1_wgrad, "pw16_bwd": drive_pw16_bwd,
+           "gnorm_fwd": drive_gnorm_fwd, "gnorm_bwd": drive_gnorm_bwd, "pw16_bwd_norm": drive_gn_head}
 
 
 def table_rows():
@@ -3009,9 +3592,10 @@ def table_rows():
 
 def _row_ident(wl, k):
     """what makes a row a repeat of an earlier workload's: the key, the flags its calls pass, the norm groups a conv driver runs the
-    layer behind with, and -- for the pack rows, which drive a whole network -- the network"""
+    layer behind with, -- for the pack rows, which drive a whole network -- the network, and for the ops that read or feed a norm table
+    (GN_TABLE_OPS) whether that table is a GroupNorm table: the same key then means another thing"""
     return (k, tuple(variants_of(wl, k)), step_groups(wl) if k[0] == "conv3_dgrad_bwdstats" else stats_fused(wl, k) if k[0] == "conv3_fwd_stats" else None,
-            network_of(wl) if k[0].endswith("pack_many") else None)
+            network_of(wl) if k[0].endswith("pack_many") else None, "gn" if is_gn(wl) and k[0] in GN_TABLE_OPS else None)
 
 
 def driven_rows():
@@ -3091,9 +3675,9 @@ def reduce_key(key, f=8):
 _VARIANT_OPS = ("norm_fwd", "norm_bwd", "down_fwd", "down_dgrad", "up_fwd", "up_dgrad", "k2_fwd_stats", "k2_wgrad", "pw_fwd",
                 "norm_fwd_slabs", "norm_bwd_slabs", "mix_box", "conv3_c1_norm_fwd", "conv3_c1_norm_bwd_wgrad", "pw16_fwd_norm",
                 "pw16_bwd_norm_bwd", "mixloss_pair_fwd", "mixloss_pair_bwd", "mixloss_fwd", "mixloss_bwd", "norm_eval",
-                "norm_fwd_res", "norm_bwd_res", "norm_eval_res", "conv3_c1_wgrad", "pw16_bwd")
+                "norm_fwd_res", "norm_bwd_res", "norm_eval_res", "conv3_c1_wgrad", "pw16_bwd", "gnorm_fwd", "gnorm_bwd", "pw16_bwd_norm")
 _FLAG_ORDER = ("chan_scale", "elem_mask", "partial", "bcast", "no_dres", "residual", "stats_only", "out_slab", "accumulate", "dw_accumulate",
-               "norm_accumulate", "out", "mask", "g_dev")
+               "norm_accumulate", "out", "mask", "g_dev", "dbias")
 
 
 def _variant_flags(name, kw):
@@ -3121,6 +3705,8 @@ def _variant_flags(name, kw):
     if out is not None:
         f.append("out")
     f += [n for n in ("mask", "g_dev") if kw.get(n) is not None]
+    if name == "gnorm_bwd" and kw.get("dbias") is not None:      # the conv-bias gradient buffer (VNet._backward_impl: L.cout > 16)
+        f.append("dbias")
     return tuple(f)
 
 
@@ -3679,6 +4265,162 @@ STEP_VARIANTS = {   # {workload: {key: flag sets the step uses}} (record_step_va
         ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 0): ((),),
         ('up_fwd', ((4, 56, 56, 40, 32), (4096,), (16,)), (16,), 0): ((),),
     },
+    "lagn": {
+        ('down_fwd', ((2, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((2, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((2, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((2, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_dgrad', ((2, 7, 7, 5, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 14, 14, 10, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 28, 28, 20, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 56, 56, 40, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('up_fwd', ((2, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((2, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((2, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_dgrad', ((2, 14, 14, 10, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((2, 28, 28, 20, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((2, 56, 56, 40, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((2, 112, 112, 80, 16), (4096,)), (32,), 1): ((),),
+        ('k2_fwd_stats', ((2, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 2), 1): ((),),
+        ('k2_wgrad', ((2, 7, 7, 5, 256), (2, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 14, 14, 10, 128), (2, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 28, 28, 20, 64), (2, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 56, 56, 40, 32), (2, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 112, 112, 80, 16), (2, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0): (('out',),),
+        ('pw16_fwd_norm', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1, 2), 0): (('chan_scale',),),
+        ('mixloss_pair_fwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): ((),),
+        ('mixloss_pair_bwd', ((2, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): (('out', 'g_dev'),),
+        ('conv3_c1_wgrad', ((2, 112, 112, 80, 1), (2, 112, 112, 80, 16), (16, 1, 3, 3, 3)), (3,), 1): (('accumulate',),),
+        ('gnorm_fwd', ((2, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((), ('chan_scale',)),
+        ('gnorm_fwd', ((2, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('gnorm_fwd', ((2, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((2, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((2, 112, 112, 80, 16), (16,), (16,)), (1,), 0): (('chan_scale', 'partial', 'stats_only'), ('partial',), ('partial', 'residual')),
+        ('gnorm_bwd', ((2, 7, 7, 5, 256), (2, 7, 7, 5, 256), (5, 2, 256)), (1, 1), 0): (('chan_scale', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((2, 14, 14, 10, 128), (2, 14, 14, 10, 128), (5, 2, 128)), (1, 1), 0): (('accumulate', 'dbias'),),
+        ('gnorm_bwd', ((2, 28, 28, 20, 64), (2, 28, 28, 20, 64), (5, 2, 64)), (1, 1), 0): (('partial', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((2, 56, 56, 40, 32), (2, 56, 56, 40, 32), (5, 2, 32)), (1, 1), 0): (('partial', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((2, 112, 112, 80, 16), (2, 112, 112, 80, 16), (5, 2, 16)), (1, 1), 0): (('chan_scale', 'accumulate'), ('accumulate',)),
+        ('pw16_bwd_norm', ((2, 112, 112, 80, 16), (5, 2, 16), (2, 16)), (2, 1), 0): (('chan_scale', 'accumulate'),),
+    },
+    "lagn_pre": {
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_dgrad', ((1, 7, 7, 5, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 14, 14, 10, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 28, 28, 20, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((1, 56, 56, 40, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_dgrad', ((1, 14, 14, 10, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((1, 28, 28, 20, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((1, 56, 56, 40, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((1, 112, 112, 80, 16), (4096,)), (32,), 1): ((),),
+        ('k2_wgrad', ((1, 7, 7, 5, 256), (1, 14, 14, 10, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 7, 7, 5, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 14, 14, 10, 128), (1, 28, 28, 20, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 14, 14, 10, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 28, 28, 20, 64), (1, 56, 56, 40, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 28, 28, 20, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 56, 56, 40, 32), (1, 112, 112, 80, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((1, 112, 112, 80, 16), (1, 56, 56, 40, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 1)), (), 0): ((),),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1, 2), 0): (('chan_scale',),),
+        ('mixloss_fwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): ((),),
+        ('mixloss_bwd', ((1, 112, 112, 80, 2), (1, 112, 112, 80), (1, 112, 112, 80)), (0,), 0): (('g_dev',),),
+        ('conv3_c1_wgrad', ((1, 112, 112, 80, 1), (1, 112, 112, 80, 16), (16, 1, 3, 3, 3)), (3,), 1): (('accumulate',),),
+        ('gnorm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((), ('chan_scale',)),
+        ('gnorm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('gnorm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0): (('chan_scale', 'partial', 'stats_only'), ('partial',), ('residual',)),
+        ('gnorm_bwd', ((1, 7, 7, 5, 256), (1, 7, 7, 5, 256), (5, 1, 256)), (1, 1), 0): (('chan_scale', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((1, 14, 14, 10, 128), (1, 14, 14, 10, 128), (5, 1, 128)), (1, 1), 0): (('accumulate', 'dbias'),),
+        ('gnorm_bwd', ((1, 28, 28, 20, 64), (1, 28, 28, 20, 64), (5, 1, 64)), (1, 1), 0): (('accumulate', 'dbias'),),
+        ('gnorm_bwd', ((1, 56, 56, 40, 32), (1, 56, 56, 40, 32), (5, 1, 32)), (1, 1), 0): (('partial', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((1, 112, 112, 80, 16), (1, 112, 112, 80, 16), (5, 1, 16)), (1, 1), 0): (('chan_scale', 'accumulate'), ('accumulate',)),
+        ('pw16_bwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (1, 16)), (1, 1), 0): (('chan_scale', 'accumulate'),),
+    },
+    "lagn_val": {
+        ('down_fwd', ((1, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((1, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((1, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((1, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_fwd', ((4, 14, 14, 10, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((4, 28, 28, 20, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((4, 56, 56, 40, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((4, 112, 112, 80, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((1, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((1, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_fwd', ((1, 56, 56, 40, 32), (4096,), (16,)), (16,), 1): ((),),
+        ('up_fwd', ((4, 7, 7, 5, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((4, 14, 14, 10, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((4, 28, 28, 20, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('k2_fwd_stats', ((4, 56, 56, 40, 32), (4096,), (16,)), (1, 16, 4), 1): ((),),
+        ('pw16_fwd_norm', ((1, 112, 112, 80, 16), (5, 1, 16), (2, 16, 1, 1, 1)), (1, 1, 2), 0): ((),),
+        ('pw16_fwd_norm', ((4, 112, 112, 80, 16), (5, 4, 16), (2, 16, 1, 1, 1)), (4, 1, 2), 0): ((),),
+        ('gnorm_fwd', ((1, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((),),
+        ('gnorm_fwd', ((1, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('gnorm_fwd', ((1, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((1, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((1, 112, 112, 80, 16), (16,), (16,)), (1,), 0): (('partial',), ('partial', 'stats_only'), ('residual',)),
+        ('gnorm_fwd', ((4, 7, 7, 5, 256), (256,), (256,)), (1,), 0): ((),),
+        ('gnorm_fwd', ((4, 14, 14, 10, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('gnorm_fwd', ((4, 28, 28, 20, 64), (64,), (64,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((4, 56, 56, 40, 32), (32,), (32,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((4, 112, 112, 80, 16), (16,), (16,)), (1,), 0): (('partial',), ('partial', 'residual'), ('partial', 'stats_only')),
+    },
+    "pancreasgn": {
+        ('down_fwd', ((2, 12, 12, 12, 128), (262144,), (256,)), (256,), 1): ((),),
+        ('down_fwd', ((2, 24, 24, 24, 64), (65536,), (128,)), (128,), 1): ((),),
+        ('down_fwd', ((2, 48, 48, 48, 32), (16384,), (64,)), (64,), 1): ((),),
+        ('down_fwd', ((2, 96, 96, 96, 16), (4096,), (32,)), (32,), 1): ((),),
+        ('down_dgrad', ((2, 6, 6, 6, 256), (262144,)), (128,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 12, 12, 12, 128), (65536,)), (64,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 24, 24, 24, 64), (16384,)), (32,), 1): (('accumulate', 'out'),),
+        ('down_dgrad', ((2, 48, 48, 48, 32), (4096,)), (16,), 1): (('accumulate', 'out'),),
+        ('up_fwd', ((2, 6, 6, 6, 256), (262144,), (128,)), (128,), 1): ((),),
+        ('up_fwd', ((2, 12, 12, 12, 128), (65536,), (64,)), (64,), 1): ((),),
+        ('up_fwd', ((2, 24, 24, 24, 64), (16384,), (32,)), (32,), 1): ((),),
+        ('up_dgrad', ((2, 12, 12, 12, 128), (262144,)), (256,), 1): ((),),
+        ('up_dgrad', ((2, 24, 24, 24, 64), (65536,)), (128,), 1): ((),),
+        ('up_dgrad', ((2, 48, 48, 48, 32), (16384,)), (64,), 1): ((),),
+        ('up_dgrad', ((2, 96, 96, 96, 16), (4096,)), (32,), 1): ((),),
+        ('k2_fwd_stats', ((2, 48, 48, 48, 32), (4096,), (16,)), (1, 16, 2), 1): ((),),
+        ('k2_wgrad', ((2, 6, 6, 6, 256), (2, 12, 12, 12, 128), (256, 128, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 6, 6, 6, 256), (256, 128, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 12, 12, 12, 128), (2, 24, 24, 24, 64), (128, 64, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 12, 12, 12, 128), (128, 64, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 24, 24, 24, 64), (2, 48, 48, 48, 32), (64, 32, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 24, 24, 24, 64), (64, 32, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 48, 48, 48, 32), (2, 96, 96, 96, 16), (32, 16, 2, 2, 2)), (1,), 2): (('accumulate',),),
+        ('k2_wgrad', ((2, 96, 96, 96, 16), (2, 48, 48, 48, 32), (32, 16, 2, 2, 2)), (0,), 2): (('accumulate',),),
+        ('mix_box', ((1, 96, 96, 96, 1), (1, 96, 96, 96, 1)), (), 0): (('out',),),
+        ('pw16_fwd_norm', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 16, 1, 1, 1)), (2, 1, 2), 0): ((),),
+        ('mixloss_pair_fwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): ((),),
+        ('mixloss_pair_bwd', ((2, 96, 96, 96, 2), (1, 96, 96, 96), (1, 96, 96, 96)), (0,), 0): (('out', 'g_dev'),),
+        ('conv3_c1_wgrad', ((2, 96, 96, 96, 1), (2, 96, 96, 96, 16), (16, 1, 3, 3, 3)), (3,), 1): (('accumulate',),),
+        ('gnorm_fwd', ((2, 6, 6, 6, 256), (256,), (256,)), (1,), 0): ((),),
+        ('gnorm_fwd', ((2, 12, 12, 12, 128), (128,), (128,)), (1,), 0): ((), ('residual',)),
+        ('gnorm_fwd', ((2, 24, 24, 24, 64), (64,), (64,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((2, 48, 48, 48, 32), (32,), (32,)), (1,), 0): ((), ('partial',), ('residual',)),
+        ('gnorm_fwd', ((2, 96, 96, 96, 16), (16,), (16,)), (1,), 0): (('partial',), ('partial', 'residual'), ('partial', 'stats_only')),
+        ('gnorm_bwd', ((2, 6, 6, 6, 256), (2, 6, 6, 6, 256), (5, 2, 256)), (1, 1), 0): (('accumulate', 'dbias'),),
+        ('gnorm_bwd', ((2, 12, 12, 12, 128), (2, 12, 12, 12, 128), (5, 2, 128)), (1, 1), 0): (('accumulate', 'dbias'),),
+        ('gnorm_bwd', ((2, 24, 24, 24, 64), (2, 24, 24, 24, 64), (5, 2, 64)), (1, 1), 0): (('partial', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((2, 48, 48, 48, 32), (2, 48, 48, 48, 32), (5, 2, 32)), (1, 1), 0): (('partial', 'accumulate', 'dbias'), ('accumulate', 'dbias')),
+        ('gnorm_bwd', ((2, 96, 96, 96, 16), (2, 96, 96, 96, 16), (5, 2, 16)), (1, 1), 0): (('accumulate',),),
+        ('pw16_bwd_norm', ((2, 96, 96, 96, 16), (5, 2, 16), (2, 96, 96, 96, 2)), (2, 1), 0): (('accumulate',),),
+    },
 }
 
 
@@ -3690,10 +4432,17 @@ def variants_of(wl, key):
 def run_row(ops, dev, wl, key, g, table_key=None):
     """one row through its driver; table_key: the STEP_KEYS row whose variants apply where `key` is its reduced twin"""
     fn = DRIVERS[key[0]]
+    gn = is_gn(wl)
+    if gn and fn is drive_head:
+        fn = drive_gn_head
+    if fn in (drive_gnorm_fwd, drive_gnorm_bwd, drive_gn_head):
+        return fn(ops, dev, key, g, variants_of(wl, table_key or key), wl=wl, table_key=table_key or key)
     if key[0] in _VARIANT_OPS:
-        return fn(ops, dev, key, g, variants_of(wl, table_key or key))
+        return fn(ops, dev, key, g, variants_of(wl, table_key or key), **({"gn": True} if gn and fn is drive_k2 else {}))
     if fn is drive_pack_many:
         return fn(ops, dev, key, g, wl)
     if fn is drive_conv:
-        return fn(ops, dev, key, g, step_groups(wl), stats_fused(wl, table_key or key) if key[0] == "conv3_fwd_stats" else True)
+        return fn(ops, dev, key, g, step_groups(wl), stats_fused(wl, table_key or key) if key[0] == "conv3_fwd_stats" else True, gn=gn)
+    if fn is drive_c1_stats:
+        return fn(ops, dev, key, g, gn=gn)
     return fn(ops, dev, key, g)

@@ -53,6 +53,12 @@ def test_own_pass_edges(emu_ops):
     S.check_own_pass_edges(emu_ops, CPU)
 
 
+@pytest.mark.parametrize("case", S.OWN_BLOCK_CASES, ids=lambda c: f"N{c[0]}-C{c[1]}-nb{c[3]}")
+def test_own_blocks(emu_ops, case):
+    """part H (a) .. (f); the sample past the library's own apply-grid cap (check_apply_past_cap) is left to the device"""
+    S.check_own_blocks(emu_ops, CPU, case)
+
+
 def test_route_census(emu_ops):
     S.check_route_census(emu_ops)
 

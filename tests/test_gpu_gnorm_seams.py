@@ -48,5 +48,14 @@ def test_own_pass_edges(gpu_ops, dev):
     S.check_own_pass_edges(gpu_ops, dev)
 
 
+@pytest.mark.parametrize("case", S.OWN_BLOCK_CASES, ids=lambda c: f"N{c[0]}-C{c[1]}-nb{c[3]}")
+def test_own_blocks(gpu_ops, dev, case):
+    S.check_own_blocks(gpu_ops, dev, case)
+
+
+def test_apply_past_cap(gpu_ops, dev):
+    S.check_apply_past_cap(gpu_ops, dev)
+
+
 def test_route_census(gpu_ops):
     S.check_route_census(gpu_ops)

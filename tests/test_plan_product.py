@@ -20,7 +20,7 @@ VOCAB = {"conv3_c1_norm_fwd", "conv3_c1_fwd_stats", "conv3_c1_fwd", "conv3_fwd_r
          "conv3_c1_norm_bwd", "conv3_c1_norm_bwd_wgrad", "conv3_dgrad_bwdstats", "k2_dgrad_bwdstats", "down_dgrad", "up_dgrad"}
 ON_INPUT = {"conv3_c1_norm_fwd", "up_fwd_norm", "conv3_c1_norm_bwd", "conv3_c1_norm_bwd_wgrad", "up_norm_bwd"}      # first operand: the layer's input
 LA, PANCREAS = (112, 112, 80), (96, 96, 96)
-# workload: (variant, has_residual, extents, passes); a pass: (N, groups, mode) -- "teacher": training mode under no_grad, "student": a
+# workload: (variant, has_residual, extents, passes[, normalization: the variant's own unless given]); a pass: (N, groups, mode) -- "teacher": training mode under no_grad, "student": a
 # saving forward with its backward, "eval": model.eval() under no_grad.  Batches and extents are those of product_ops.make_step: a
 # self-training step runs teacher and student with groups=2 at half the batch, a pre-training step one saving pass on one sample, a
 # validation pass one full chunk of four patches and a remainder chunk of one
@@ -35,6 +35,10 @@ WORKLOADS = {
     "la_val": ("la", False, LA, ((4, 1, "eval"), (1, 1, "eval"))),
     "lares_val": ("la", True, LA, ((4, 1, "eval"), (1, 1, "eval"))),
     "pancreas_val": ("pancreas", False, PANCREAS, ((4, 1, "eval"), (1, 1, "eval"))),
+    "lagn": ("la", False, LA, ((2, 2, "teacher"), (2, 2, "student")), "groupnorm"),
+    "lagn_pre": ("la", False, LA, ((1, 1, "student"),), "groupnorm"),
+    "lagn_val": ("la", False, LA, ((4, 1, "eval"), (1, 1, "eval")), "groupnorm"),
+    "pancreasgn": ("pancreas", False, PANCREAS, ((2, 2, "teacher"), (2, 2, "student")), "groupnorm"),
 }
 # the wrappers that run their plain op themselves where their rows query answers 0 (the planner's record holds that answer in `rows`): a
 # REPLAYED step keys the launches by the plain op alone, an EAGER pass (validation) keys the wrapper's call and, inside it, the plain op's
@@ -78,8 +82,8 @@ def planned_pairs(net, N, sp, groups, mode):
 
 @pytest.mark.parametrize("workload", sorted(WORKLOADS))
 def test_planner_against_product_table(product_ops, workload):
-    variant, res, sp, passes = WORKLOADS[workload]
-    net = VNet(n_channels=1, n_classes=2, normalization="batchnorm" if variant == "la" else "instancenorm", has_dropout=variant == "la",
+    variant, res, sp, passes, *norm = WORKLOADS[workload]
+    net = VNet(n_channels=1, n_classes=2, normalization=norm[0] if norm else "batchnorm" if variant == "la" else "instancenorm", has_dropout=variant == "la",
                has_residual=res, variant=variant).set_ops(product_ops)
     planned = set()
     for N, groups, mode in passes:

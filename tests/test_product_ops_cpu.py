@@ -64,13 +64,13 @@ def _reduced_rows():
     return rows
 
 
-# the LA rows (self-training, pre-training, validation; plain and residual V-Net) run in the default CPU suite; the pancreas / ACDC /
-# batch-8 rows (same drivers, other shapes) with BCP_EXTENDED=1.
+# the LA rows (self-training, pre-training, validation; plain, residual and GroupNorm V-Net) run in the default CPU suite; the pancreas /
+# ACDC / batch-8 rows (same drivers, other shapes; pancreasgn among them) with BCP_EXTENDED=1.
 # At the reduced shapes the dispatch may differ from the in-step one: a conv3_fwd_raw row falls back to conv3_fwd where the shape is
 # not served raw, and where a conv leaves no fused statistics (rows == 0) the fwd_stats / dgrad_bwdstats rows and the norm rows' "partial"
 # epilogue run without them.  These rows check the drivers and references on the simulator; the route itself is asserted on the device
 # (tests/test_gpu_product_ops.py: each row must launch its key, and the drivers require the fused routes there).
-@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] in ("la", "la_pre", "la_val", "lares", "lares_pre", "lares_val") else pytest.mark.extended) for r in _reduced_rows()],
+@pytest.mark.parametrize("wl,key,rkey", [pytest.param(*r, marks=() if r[0] in ("la", "la_pre", "la_val", "lares", "lares_pre", "lares_val", "lagn", "lagn_pre", "lagn_val") else pytest.mark.extended) for r in _reduced_rows()],
                          ids=[P.row_id(r[0], r[1]) for r in _reduced_rows()])
 def test_product_op_reduced_on_simulator(emu_ops, wl, key, rkey):  # noqa: F811
     g = torch.Generator().manual_seed(5)
@@ -151,11 +151,12 @@ def test_every_step_op_has_a_driver():
     row is driven under its own workload or is the repeat of a row driven under an earlier one (same key, same flags), and the only
     rows outside the table are the keys a statistics-only norm call uses"""
     assert sorted(P.STEP_KEYS) == sorted(["la", "pancreas", "acdc", "la_pre", "pancreas_pre", "acdc_pre", "la_val", "pancreas_val", "acdc_val", "la8",
-                                          "lares", "lares_pre", "lares_val"])
+                                          "lares", "lares_pre", "lares_val", "lagn", "lagn_pre", "lagn_val", "pancreasgn"])
     assert {k[0] for _, k in P.table_rows()} - set(UNDRIVEN) <= set(P.DRIVERS)
     rows = P.driven_rows()
-    assert len(P.table_rows()) == 671 + 221 and len(set(rows)) == len(rows)          # (221: the three residual workloads)
-    assert len([1 for wl, _ in P.table_rows() if not wl.startswith("lares")]) == 671
+    assert len(P.table_rows()) == 671 + 221 + 234 and len(set(rows)) == len(rows)    # (221: the three residual workloads, 234: the four GroupNorm ones)
+    assert len([1 for wl, _ in P.table_rows() if not wl.startswith("lares") and not P.is_gn(wl)]) == 671
+    assert [len(P.STEP_KEYS[wl]) for wl in ("lagn", "lagn_pre", "lagn_val", "pancreasgn")] == [63, 59, 49, 63]
     first = [(wl, k) for wl, k in P.table_rows() if wl in ("la", "pancreas", "acdc")]
     assert len(first) == 223 and set(first) <= set(rows)                      # (the self-training table is driven as before)
     driven = {P._row_ident(wl, k) for wl, k in rows}
@@ -164,6 +165,11 @@ def test_every_step_op_has_a_driver():
     assert all(k[0] == "norm_fwd" for k in extra), extra
     for op in ("norm_fwd_res", "norm_bwd_res", "norm_eval_res", "axpy", "conv3_c1_fwd_stats", "conv3_c1_wgrad", "pw16_bwd"):      # the residual V-Net's
         assert any(k[0] == op and wl.startswith("lares") for wl, k in rows), op
+    for op in ("gnorm_fwd", "gnorm_bwd", "pw16_bwd_norm", "pw16_fwd_norm", "conv3_dgrad_bwdstats", "k2_fwd_stats", "conv3_c1_fwd_stats"):      # the GroupNorm V-Nets'
+        assert any(k[0] == op and P.is_gn(wl) for wl, k in rows), op
+    gn_keys = {(wl, k) for wl, k in P.table_rows() if P.is_gn(wl) and k[0] in ("gnorm_fwd", "gnorm_bwd", "pw16_bwd_norm", "pw16_fwd_norm")}
+    gn_driven = {P._row_ident(wl, k) for wl, k in rows if P.is_gn(wl)}     # (every GroupNorm launch a step records is driven under a GroupNorm workload)
+    assert len(gn_keys) == 48 and all(P._row_ident(wl, k) in gn_driven for wl, k in gn_keys)
     for op in ("norm_eval", "sw_accumulate", "sw_finish", "overlap_counts", "plabel_argmax4", "mixloss_fwd", "mixloss_bwd", "conv3_c1_fwd", "pw16_fwd",
                "copy_channels"):
         assert any(k[0] == op for _, k in rows), op
@@ -443,6 +449,45 @@ def test_residual_driver_rejects_near_miss_reference(emu_ops, miss, op, wl):  # 
     assert rows, (op, wl)
     n = 0
     for w, key in rows:                       # (norm_bwd_res has two 16-channel rows: the full and the broadcast residual)
+        rkey = P.reduce_key(key)
+        P.run_row(emu_ops, torch.device("cpu"), w, rkey, torch.Generator().manual_seed(5), table_key=key)
+        P.NEAR_MISS, P.NEAR_MISS_HITS = miss, 0
+        try:
+            try:
+                P.run_row(emu_ops, torch.device("cpu"), w, rkey, torch.Generator().manual_seed(5), table_key=key)
+                assert P.NEAR_MISS_HITS == 0, f"{miss}: the near-miss reference was accepted at {rkey}"
+            except AssertionError as e:
+                assert P.NEAR_MISS_HITS > 0 and "accepted" not in str(e), e
+                n += 1
+        finally:
+            P.NEAR_MISS = None
+    assert n >= 1, f"{miss}: no {op} row applies it"
+
+
+# -------------------------------------------------------------------------------------------------- can the GroupNorm drivers fail?
+# (near-miss, the op of the GroupNorm row driven, its workload, the channel count of the row)
+GN_NEAR_MISSES = [("gn_channel_statistics", "gnorm_fwd", "lagn", 32), ("gn_channel_statistics", "gnorm_bwd", "lagn", 32),
+                  ("gn_channel_statistics", "conv3_dgrad_bwdstats", "lagn", 32),
+                  ("gn_shifted_table", "gnorm_fwd", "lagn", 16), ("gn_shifted_table", "gnorm_bwd", "lagn", 16),
+                  ("gn_shifted_table", "pw16_fwd_norm", "lagn", 16), ("gn_shifted_table", "pw16_bwd_norm", "lagn", 16),
+                  ("gn_block_dropped", "gnorm_fwd", "lagn", 16), ("gn_block_dropped", "gnorm_bwd", "lagn", 32),
+                  ("gn_row4_flipped", "gnorm_bwd", "lagn", 32)]
+
+
+def test_gn_near_misses_cover_the_list():
+    assert {n for n, _, _, _ in GN_NEAR_MISSES} == set(P.GN_NEAR_MISSES)
+
+
+@pytest.mark.parametrize("miss,op,wl,C", GN_NEAR_MISSES, ids=[f"{m}-{o}" for m, o, _, _ in GN_NEAR_MISSES])
+def test_gn_driver_rejects_near_miss_reference(emu_ops, miss, op, wl, C):  # noqa: F811
+    """each GroupNorm driver on the simulator at the reduced shape of its row: with the right fp64 reference the row passes; with one that
+    is wrong the way a plausible kernel would be -- every channel normalised with its own statistics, sample n with sample n - 1's table,
+    one block of the statistics pass left out, row 4's sign flipped in the conv-bias gradient -- the driver's own bound on the driver's
+    own inputs must reject the (correct) kernel output"""
+    rows = [(w, k) for w, k in P.table_rows() if w == wl and k[0] == op and k[1][0][-1] == C]
+    assert rows, (op, wl)
+    n = 0
+    for w, key in rows:
         rkey = P.reduce_key(key)
         P.run_row(emu_ops, torch.device("cpu"), w, rkey, torch.Generator().manual_seed(5), table_key=key)
         P.NEAR_MISS, P.NEAR_MISS_HITS = miss, 0
