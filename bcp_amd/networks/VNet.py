@@ -21,13 +21,14 @@ block_eight(2x32) up+x1 block_nine(16) [Dropout3d] out_conv(16->n_classes, 1x1x1
 """
 from __future__ import annotations
 
-import math
+import functools
 
 import torch
 import torch.nn as nn
 
 from .. import hip_ops as H
-from ._hipnet import BNP, GNP, ConvP, HipNet, Holder, NetFn, Seq, contrastive_heads
+from ._hipnet import (BNP, GNP, ConvP, HipNet, Holder, NetFn, Seq, _BwdRoute, _Plan, _Route, _SavedLayer, _norm_params, contrastive_heads,
+                      plan_conv3_dgrad, plan_conv3_fwd)
 
 
 class UnsupportedConfiguration(NotImplementedError, AssertionError):
@@ -46,49 +47,6 @@ class _Layer:
         self.block_first = False  # has_residual: first 3x3x3 layer of a block -- its input is the block input the closing layer adds
 
 
-class _Route:
-    """one layer's forward route (VNet.plan_forward).  producer / norm: the names of the Ops methods the forward calls -- one name twice where
-    one op is both (the recomputing fusions).  nslabs: split-K slabs the producer leaves raw (1: a plain tensor); rows: statistics rows per
-    group its epilogue leaves (0: none -- conv3_fwd_stats / conv3_c1_fwd_stats then run their plain conv themselves); stats_only: the norm writes its table only, the fused head applies it; dropout: a Dropout3d
-    channel scale rides in the norm's epilogue; xshape / yshape: the producer's input and output"""
-    __slots__ = ("producer", "norm", "stats_only", "nslabs", "rows", "dropout", "closing", "xshape", "yshape")
-
-    @property
-    def keeps_y(self):
-        """the layer writes its pre-norm tensor (a recomputing fusion does not)"""
-        return self.producer != self.norm
-
-    @property
-    def bwdstats_ok(self):
-        """the dgrad behind this layer may leave its norm's backward statistics in its epilogue: there is a pre-norm tensor to read, no
-        dropout epilogue, and the ReLU pattern follows from z alone (not behind the closing layer of a residual block)"""
-        return self.keeps_y and not self.dropout and not self.closing
-
-
-class _BwdRoute:
-    """one layer's backward route (VNet.plan_backward).  norm: the op that does the norm's backward (the head's, where that goes through);
-    partial: it takes the backward-statistics rows the dgrad behind it left; dgrad: the layer's own dgrad op (None: the first layer), which
-    writes nslabs raw split-K slabs (1: a plain tensor) and leaves `rows` statistics rows per group for the layer in front (0: none -- conv3_dgrad_bwdstats then runs the plain dgrad itself)"""
-    __slots__ = ("norm", "partial", "dgrad", "nslabs", "rows")
-
-
-class _Plan:
-    """one pass's routes: G normalisation groups, the head's op, a _Route per layer, running-statistics updates to count"""
-    __slots__ = ("G", "head", "layers", "bn_ticks")
-
-    def __init__(self, G, head, layers, bn_ticks):
-        self.G, self.head, self.layers, self.bn_ticks = G, head, layers, bn_ticks
-
-
-class _SavedLayer:
-    """what a layer's backward reads: input, pre-norm tensor (None: recomputed), statistics, Dropout3d channel scale, the block input a
-    closing layer added (has_residual) and the layer's route"""
-    __slots__ = ("x", "y", "stats", "cs", "r_in", "route")
-
-    def __init__(self, x, y, stats, cs, r_in, route):
-        self.x, self.y, self.stats, self.cs, self.r_in, self.route = x, y, stats, cs, r_in, route
-
-
 class _Saved:
     """what a saving forward hands to its backward -- one object per pass (launch plans key the backward on its identity)"""
     __slots__ = ("plan", "layers", "head_in")
@@ -105,14 +63,8 @@ class _Saved:
         return (rows + [(self.head_in,)])[i]
 
 
-def _norm_params(bn):
-    """(gamma, beta, running mean, running variance) of a BatchNorm layer; InstanceNorm has no module: four Nones"""
-    return (None,) * 4 if bn is None else (bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
-
-
 class VNet(HipNet):
     UP_RECOMPUTE_GRAD = False   # (round 6) the recomputing transposed conv + norm (library option up_recompute) also in forwards that save for a backward pass: measured slower there (both passes of the norm's backward recompute the conv); forwards WITHOUT a backward pass -- the teacher's -- take it wherever the library serves the shape
-    WGRAD_DEFER = 2      # (round 6) small layers' weight gradients cross to the side stream in batches of this many layers (1: every layer forks, rounds 2-5)
     fuse_c1 = True       # first layer: conv + norm + ReLU with recompute (bcp_conv3_c1_norm_fwd / _bwd); False: conv -> y -> norm passes
     fuse_head = True     # the 1x1x1 head applies the last conv's norm + ReLU + Dropout3d itself (bcp_pw16_fwd_norm); False: separate apply pass
 
@@ -285,7 +237,7 @@ class VNet(HipNet):
             r.xshape = (N,) + sp + (L.cin,)
             sp = tuple(e // 2 for e in sp) if L.kind == "dw" else tuple(2 * e for e in sp) if L.kind == "up" else sp
             r.yshape = (N,) + sp + (L.cout,)
-            r.closing, r.dropout, r.stats_only, r.nslabs, r.rows = L.closing, dropout and L.drop is not None, li == last and fuse_head, 1, 0
+            r.closing, r.dropout, r.stats_only = L.closing, dropout and L.drop is not None, li == last and fuse_head
             # a fusion whose norm reads something else than a plain pre-norm tensor: training-mode BatchNorm / InstanceNorm only, and never
             # where another op reads that tensor -- the closing layer of a residual block (bcp_norm_fwd_res / _eval_res apply relu(z + r)
             # themselves) and the layer in front of the fused head
@@ -299,17 +251,8 @@ class VNet(HipNet):
                     r.producer, r.rows = "conv3_c1_fwd_stats", ops.conv3_c1_stat_rows(r.xshape, 3, G)
                 else:
                     r.producer = "conv3_c1_fwd"
-            elif L.kind == "c3":
-                # deep levels (<= 4096 rows per normalisation group) whose conv runs split-K: the conv leaves its raw slabs and the norm's
-                # statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs) -- no slab-sum launch
-                if fusable and ops.norm_slabs_ok(G, N * sp[0] * sp[1] * sp[2] // G, L.cout):
-                    r.nslabs = max(ops.conv3_nslabs(r.xshape, L.cout, 3), 1)
-                if r.nslabs > 1:
-                    r.producer = "conv3_fwd_raw"
-                elif batch_stats or L.bn is None:
-                    r.producer, r.rows = "conv3_fwd_stats", ops.conv3_stat_rows(r.xshape, L.cout, 3, G)
-                else:                                     # eval-mode BatchNorm needs no batch statistics
-                    r.producer = "conv3_fwd"
+            elif L.kind == "c3":                          # (eval-mode BatchNorm needs no batch statistics)
+                plan_conv3_fwd(ops, r, 3, G, slabs=fusable, stats=batch_stats or L.bn is None)
             elif L.kind == "up" and recompute and (not save or self.UP_RECOMPUTE_GRAD) and ops.up_norm_rows(r.xshape, L.cout, G) > 0:
                 # (round 6) transposed conv + norm + ReLU + skip add with recompute (bcp_up_fwd_norm): the pre-norm tensor is never written
                 r.producer = "up_fwd_norm"
@@ -364,20 +307,10 @@ class VNet(HipNet):
             # the consumer of this layer's dgrad is the norm backward of the layer in front.  has_residual: the dgrad of a block's FIRST layer
             # is joined with the shortcut's gradient first -- a plain tensor, and no statistics taken from it in front of the join
             prev = R[li - 1] if li > 0 and not L.block_first else None
-            b.nslabs, b.rows = 1, 0
             if L.kind == "c1":
                 b.dgrad = None
             elif L.kind == "c3":
-                # deep levels: the raw split-K slabs (no slab-sum launch); else, without a dropout epilogue in front, the dgrad epilogue
-                # leaves the backward statistics (bcp_conv3_dgrad_bwdstats) where the shape is served
-                if prev is not None and prev.keeps_y and not gn and ops.norm_slabs_ok(G, math.prod(r.xshape) // (L.cin * G), L.cin):
-                    b.nslabs = max(ops.conv3_nslabs(r.yshape, L.cin, 3), 1)
-                if b.nslabs > 1:
-                    b.dgrad = "conv3_fwd_raw"
-                elif prev is not None and prev.bwdstats_ok:
-                    b.dgrad, b.rows = "conv3_dgrad_bwdstats", ops.conv3_bwdstat_rows(r.yshape, L.cin, 3, G)
-                else:
-                    b.dgrad = "conv3_fwd"
+                plan_conv3_dgrad(ops, b, r, prev, 3, G, slabs=not gn)
             else:
                 # (round 6) bcp_down_dgrad_bwdstats / bcp_up_dgrad_bwdstats where the shape is served: no k_col_partial<1> pass over (y, da)
                 if prev is not None and prev.bwdstats_ok:
@@ -499,24 +432,7 @@ class VNet(HipNet):
         else:
             dh = ops.pw16_bwd(saved.head_in, dlogits, self._out.weight.data, self._out.weight.grad, self._out.bias.grad, accumulate=True)
         skip_grads = []
-        pend = []
-
-        def flush_wgrads():
-            if not pend:
-                return
-            with self._wgrad_stream(*[t for j in pend for t in (j[2], j[1])]):
-                for kind, x_in_, dy_, gw_, acc_, _ in pend:
-                    if kind == "c1":
-                        ops.conv3_c1_wgrad(x_in_, dy_, gw_, 3, accumulate=acc_)
-                    elif kind == "c3":
-                        ops.conv3_wgrad(x_in_, dy_, gw_, 3, accumulate=acc_)
-                    elif kind == "dw":
-                        ops.k2_wgrad(x_in_, dy_, gw_, H.WG_DOWN, accumulate=acc_)
-                    else:
-                        ops.k2_wgrad(x_in_, dy_, gw_, H.WG_UP, accumulate=acc_)
-            for j in pend:       # (data parallelism: the flat gradient buffer is final from this layer's first parameter on -- bucket hook)
-                self._grads_final_from(j[5], j[2])
-            pend.clear()
+        self._wg_pend = []
         bpart, bnb = None, 0             # backward-statistics partials of THIS layer's norm, left by the dgrad that produced dh
         for li in range(len(self._layers) - 1, -1, -1):
             L, s, r = self._layers[li], saved.layers[li], routes[li]
@@ -537,7 +453,7 @@ class VNet(HipNet):
             elif n == "conv3_c1_norm_bwd_wgrad":      # no dy, no launch left behind the main stream's last one
                 ops.conv3_c1_norm_bwd_wgrad(x_in, w.data, L.conv.bias.data, 3, G, stats, da, H.ACT_RELU, w.grad, dg, db, L.bn is not None,
                                             dw_accumulate=True)
-                flush_wgrads()
+                self._wgrad_flush()
                 self._grads_final_from(w, da)
                 break
             elif n == "conv3_c1_norm_bwd":      # the fused first layer: its pre-norm tensor is recomputed from the input
@@ -553,17 +469,14 @@ class VNet(HipNet):
             bpart, bnb = None, 0
             if L.skip_pop:
                 skip_grads.append(da)       # d(out)/d(skip) = identity: the skip source gets `da` itself
-            gw, acc = w.grad, True
             # conv biases feed a norm: behind BatchNorm / InstanceNorm their gradient is identically zero (DESIGN.md "bias gradients"); the flat
             # gradient buffer was cleared by begin_backward(), nothing to add.  (GroupNorm: gnorm_bwd above has added it.)
-            # The weight gradient of a layer has no consumer inside the backward pass: it runs on a side stream underneath
-            # the dgrad -> norm_bwd critical path (the deep levels' kernels are too small to fill 256 CUs on their own).
-            # (round 6) every fork onto the side stream is an event record between two kernels of the MAIN stream -- a 5-7 us gap in front of
-            # the dgrad that follows -- so the small layers' weight gradients go over in batches of WGRAD_DEFER layers behind ONE fork; the
-            # large layers (>= 2^22 elements of dy) fork at once, as before
-            pend.append((L.kind, x_in, dy, gw, acc, w))
-            if dy.numel() >= (1 << 22) or len(pend) >= self.WGRAD_DEFER:
-                flush_wgrads()
+            # The weight gradient goes to the side stream, in batches (HipNet._wgrad_later)
+            if L.kind in ("c1", "c3"):
+                wgrad, arg = ops.conv3_c1_wgrad if L.kind == "c1" else ops.conv3_wgrad, 3      # (x, dy, dw, KD)
+            else:
+                wgrad, arg = ops.k2_wgrad, H.WG_DOWN if L.kind == "dw" else H.WG_UP            # (x, dy, dw, kind)
+            self._wgrad_later(functools.partial(wgrad, x_in, dy, w.grad, arg, accumulate=True), dy, x_in, final=w)
             d = r.dgrad
             prev = saved.layers[li - 1] if li > 0 else None      # (a *_dgrad_bwdstats epilogue reads its pre-norm tensor and statistics)
             if d is None:
@@ -591,7 +504,7 @@ class VNet(HipNet):
                 # front consumes (and, behind an up layer, what skip_grads receives)
                 dh = ops.axpy(dh, dres, 1.0)
                 ops._no_amax(dh)
-        flush_wgrads()
+        self._wgrad_flush()
         self._join_wgrad_stream(dlogits)
         return None
 

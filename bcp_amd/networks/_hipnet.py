@@ -4,13 +4,14 @@ autograd bridge (one Function node per network call; the whole backward is sched
 """
 from __future__ import annotations
 
+import math
 import os
 import weakref
 
 import torch
 import torch.nn as nn
 
-from ..hip_ops import Ops
+from ..hip_ops import ACT_RELU, Ops
 
 
 class ConvP(nn.Module):
@@ -67,6 +68,98 @@ def contrastive_heads(owner: nn.Module, n_sel: int):
         for c in range(n_sel):
             sel = nn.Sequential(nn.Linear(32, 32), nn.BatchNorm1d(32), nn.LeakyReLU(negative_slope=0.2, inplace=True), nn.Linear(32, 1))
             owner.__setattr__(fam + str(c), sel)
+
+
+# ---- the schedule's records: what a network's launch-free planner (VNet / UNet_2d plan_forward, plan_backward) hands to its executors
+class _Route:
+    """one layer's forward route.  producer / norm: the names of the Ops methods the forward calls -- one name twice where one op is both
+    (the recomputing fusions), norm None for a conv nothing normalises.  nslabs: split-K slabs the producer leaves raw (1: a plain tensor);
+    rows: statistics rows per group its epilogue leaves (0: none -- conv3_fwd_stats / conv3_c1_fwd_stats then run their plain conv
+    themselves); stats_only: the norm writes its table only, the fused head applies it; dropout: a dropout operand rides in the norm's
+    epilogue -- a Dropout3d channel scale, or with elem_mask an elementwise keep mask (the U-Net's nn.Dropout); act: the activation
+    (hip_ops.ACT_*); out_slab: the norm writes into the leading channels of a concat buffer; xshape / yshape: the producer's input and output"""
+    __slots__ = ("producer", "norm", "stats_only", "nslabs", "rows", "dropout", "closing", "xshape", "yshape", "act", "elem_mask", "out_slab")
+
+    def __init__(self):
+        self.stats_only = self.dropout = self.closing = self.elem_mask = self.out_slab = False
+        self.nslabs, self.rows, self.act = 1, 0, ACT_RELU
+
+    @property
+    def keeps_y(self):
+        """the layer writes its pre-norm tensor (a recomputing fusion does not)"""
+        return self.producer != self.norm
+
+    @property
+    def bwdstats_ok(self):
+        """the dgrad behind this layer may leave its norm's backward statistics in its epilogue: there is a pre-norm tensor to read, no
+        dropout epilogue, and the activation pattern follows from z alone (not behind the closing layer of a residual block)"""
+        return self.keeps_y and not self.dropout and not self.closing
+
+
+class _BwdRoute:
+    """one layer's backward route.  norm: the op that does the norm's backward (the head's, where that goes through; None: no norm);
+    partial: it takes the backward-statistics rows the dgrad behind it left; dgrad: the layer's own dgrad op (None: the first layer), which
+    writes nslabs raw split-K slabs (1: a plain tensor) and leaves `rows` statistics rows per group for the layer in front (0: none --
+    conv3_dgrad_bwdstats then runs the plain dgrad itself)"""
+    __slots__ = ("norm", "partial", "dgrad", "nslabs", "rows")
+
+    def __init__(self):
+        self.partial, self.nslabs, self.rows = False, 1, 0
+
+
+class _Plan:
+    """one pass's routes: G normalisation groups, the head's op, a _Route per layer, running-statistics updates to count; direct (U-Net):
+    per encoder level, the block's output is written straight into the decoder's concat buffer (no copy_channels)"""
+    __slots__ = ("G", "head", "layers", "bn_ticks", "direct")
+
+    def __init__(self, G, head, layers, bn_ticks, direct=()):
+        self.G, self.head, self.layers, self.bn_ticks, self.direct = G, head, layers, bn_ticks, direct
+
+
+class _SavedLayer:
+    """what a layer's backward reads: input, pre-norm tensor (None: recomputed), statistics, the dropout operand (route.dropout: a Dropout3d
+    channel scale, or an elementwise keep mask), the block input a closing layer added (has_residual) and the layer's route"""
+    __slots__ = ("x", "y", "stats", "cs", "r_in", "route")
+
+    def __init__(self, x, y, stats, cs, r_in, route):
+        self.x, self.y, self.stats, self.cs, self.r_in, self.route = x, y, stats, cs, r_in, route
+
+
+def _norm_params(bn):
+    """(gamma, beta, running mean, running variance) of a BatchNorm layer; InstanceNorm has no module: four Nones"""
+    return (None,) * 4 if bn is None else (bn.weight.data, bn.bias.data, bn.running_mean, bn.running_var)
+
+
+def plan_conv3_fwd(ops, r, KD, G, slabs, stats):
+    """the forward producer of a 3x3(x3) conv, written into its route (xshape / yshape set).  `slabs` (a training-mode norm that may read
+    something else than a plain tensor) on a deep level -- <= 4096 rows per normalisation group -- whose conv runs split-K: the conv leaves
+    its raw slabs and the norm's statistics pass sums them (+ bias) on its way in (bcp_norm_fwd_slabs), no slab-sum launch.  Else with
+    `stats` the norm's statistics from the conv's epilogue (its rows; 0: the shape is not served), else the plain conv"""
+    cout = r.yshape[-1]
+    if slabs and ops.norm_slabs_ok(G, math.prod(r.yshape[:-1]) // G, cout):
+        r.nslabs = max(ops.conv3_nslabs(r.xshape, cout, KD), 1)
+    if r.nslabs > 1:
+        r.producer = "conv3_fwd_raw"
+    elif stats:
+        r.producer, r.rows = "conv3_fwd_stats", ops.conv3_stat_rows(r.xshape, cout, KD, G)
+    else:
+        r.producer = "conv3_fwd"
+
+
+def plan_conv3_dgrad(ops, b, r, prev, KD, G, slabs=True):
+    """the dgrad of a 3x3(x3) conv with forward route r, written into its backward route b.  prev: the route of the layer whose norm backward
+    consumes this dgrad directly (None: nothing does -- a join in between, no norm in front).  Deep levels: the raw split-K slabs, summed by
+    that norm backward's statistics pass (bcp_norm_bwd_slabs); else, where prev has no dropout epilogue, the dgrad epilogue leaves its
+    backward statistics (bcp_conv3_dgrad_bwdstats, its rows); else the plain dgrad"""
+    cin = r.xshape[-1]
+    if prev is not None and prev.keeps_y and slabs and ops.norm_slabs_ok(G, math.prod(r.xshape[:-1]) // G, cin):
+        b.nslabs = max(ops.conv3_nslabs(r.yshape, cin, KD), 1)
+    if b.nslabs > 1:
+        b.dgrad = "conv3_fwd_raw"
+    elif prev is not None and prev.bwdstats_ok:
+        b.dgrad, b.rows = "conv3_dgrad_bwdstats", ops.conv3_bwdstat_rows(r.yshape, cin, KD, G)
+    else:
+        b.dgrad = "conv3_fwd"
 
 
 class HipNet(nn.Module):
@@ -457,6 +550,35 @@ class HipNet(nn.Module):
 
     def _wgrad_stream(self, *tensors):
         return HipNet._OnSide(self, tensors)
+
+    # A layer's weight gradient has no consumer inside the backward pass: it runs on the side stream underneath the dgrad -> norm backward
+    # critical path (the deep levels' kernels are too small to fill 256 CUs on their own).  (round 6) Every fork onto the side stream is an
+    # event record between two kernels of the MAIN stream -- a 5-7 us gap in front of the dgrad that follows -- so the small layers' weight
+    # gradients go over in batches of WGRAD_DEFER launches behind ONE fork (1: every layer forks, rounds 2-5); launches on >= 2^22 elements
+    # of dy fork at once
+    WGRAD_DEFER = 2
+    _wg_pend = None
+
+    def _wgrad_later(self, launch, dy, x_in, final=None):
+        """queue `launch()` -- the weight-gradient launches of one layer, reading dy and x_in -- for the side stream.  final (data parallelism):
+        the layer's first parameter -- once the batch is on the side stream the flat gradient buffer is final from there on (bucket hook)"""
+        if self._wg_pend is None:
+            self._wg_pend = []
+        self._wg_pend.append((launch, dy, x_in, final))
+        if dy.numel() >= (1 << 22) or len(self._wg_pend) >= self.WGRAD_DEFER:
+            self._wgrad_flush()
+
+    def _wgrad_flush(self):
+        pend = self._wg_pend
+        if not pend:
+            return
+        with self._wgrad_stream(*[t for j in pend for t in (j[1], j[2])]):
+            for j in pend:
+                j[0]()
+        for j in pend:
+            if j[3] is not None:
+                self._grads_final_from(j[3], j[1])
+        pend.clear()
 
     def _join_wgrad_stream(self, like):
         if like.is_cuda and self.overlap_wgrad:

@@ -708,6 +708,7 @@ def check_unet_skip_in_concat(ops, dev, hw=(64, 64), N=4, seed=23, min_direct=3)
         finally:
             del ops.copy_channels
         copies[flag] = n[0]
+        assert n[0] == sum(not d for d in net.plan_call(N, *hw).direct), (flag, n[0])      # ... as the planner said
         res[flag] = (out.detach().cpu(), {k: p.grad.detach().cpu().clone() for k, p in net.named_parameters() if p.grad is not None})
     assert copies[False] == 4 and copies[True] <= min_direct, copies      # the four concat copies; a level served by the raw-slab norm still copies (tiny extents only)
     assert K.rel_l2(res[True][0], res[False][0]) < 1e-5, K.rel_l2(res[True][0], res[False][0])

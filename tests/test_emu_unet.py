@@ -6,6 +6,9 @@ import pytest
 import torch
 
 import net_checks as NC
+import unet_plan_checks as UP
+from bcp_amd import _lib
+from bcp_amd.hip_ops import Ops
 from test_emu_kernels import emu_ops  # noqa: F401  (fixture)
 
 CPU = torch.device("cpu")
@@ -87,6 +90,23 @@ def test_acdc_five_step_trajectory(emu_ops, golden_dir):
 @pytest.mark.extended
 def test_unet_standard_regime_gradients_on_hip_pattern(emu_ops):
     NC.check_unet_pattern_grads(emu_ops, CPU)
+
+
+# (a saving 64 x 64 pass with its backward takes the simulator 20 s: those four run with BCP_EXTENDED=1 here, and on the device every time)
+@pytest.mark.parametrize("case", [pytest.param(c, marks=pytest.mark.extended) if UP.CASES[c][0] == (64, 64) and UP.CASES[c][2] == "train" else c
+                                  for c in sorted(UP.CASES)])
+def test_planned_equals_ran(emu_ops, case):
+    UP.check_planned_equals_ran(emu_ops, CPU, case)
+
+
+def test_routes_reached(emu_ops):
+    UP.check_routes_reached(emu_ops)
+
+
+def test_routes_reached_product_library():
+    """the gfx950 library's shape queries give the same set: no GPU needed"""
+    assert os.path.exists(_lib.LIB_PATH), "libbcp_hip.so missing -- run __graft_entry__.build()"
+    UP.check_routes_reached(Ops(_lib.Binding(_lib.LIB_PATH), allow_cpu=True))
 
 
 def test_launch_plan_hygiene(emu_ops):

@@ -9,6 +9,7 @@ import torch
 import bcp_oracle as O
 import kernel_checks as K
 import net_checks as NC
+import unet_plan_checks as UP
 
 pytestmark = pytest.mark.gpu
 
@@ -144,6 +145,11 @@ def test_acdc_five_step_trajectory_full_size(ops, golden_dir):
             print("acdc_traj5f step %d: |hip - ref32| %.2e  |hip - ref64| %.2e  (reference 32 vs 64: %.2e)  pseudo-label sum diff %.0f (reference: %.0f)" % r)
     for it, d32, d64, dr, pl, plr in rep:
         assert d32 <= 1e-4 and d64 <= 1e-4, (it, d32, d64)
+
+
+@pytest.mark.parametrize("case", sorted(UP.CASES))
+def test_planned_equals_ran(ops, case):
+    UP.check_planned_equals_ran(ops, DEV, case)
 
 
 def test_launch_plan_hygiene(ops):
