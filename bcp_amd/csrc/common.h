@@ -89,6 +89,8 @@ struct Options {
   int c3d16_form = 1;       // persistent 16-output-channel k_c3d on two fp16 planes (the 16 -> 16 layers): 1 = the weight fragments of the one cin chunk
                             // copied into the LDS once per workgroup, the tap loop issues no global load but the halo prefetch; 0 = fragments
                             // streamed from global memory one tap pair ahead (round 6).  Bit-identical results
+  int c3d32_form = 1;       // 32-channel-slab k_c3d on two fp16 planes (the 32 -> 32 layers, 3-D): 1 = persistent, the next tile's halo under the current
+                            // tile's tap pairs, one statistics row per TILE as before; 0 = one tile per workgroup.  Bit-identical results, same row counts
   int whatif = 0;           // MEASUREMENT ONLY (wrong results): bit 0 = no finalize launches of the norm layers, bit 1 = no finalize and no apply launches where rows per group <= 4096, bit 2 = no largest-CC launches, bit 3 = no conv / k2 weight-gradient launches, bit 4 = no forward / backward apply pass at >= 100000 rows per group, bit 5 = no backward statistics pass there (prices a change before it is built)
   int wgrad_b6_levels = 15; // bit 3: 2-D; bit 2: also the 16-channel slabs (one n-tile per wave): 187 vs 270 us alone, 7.28 vs 7.36 ms per step
 };
@@ -137,6 +139,19 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 typedef __attribute__((address_space(3))) void* bcp_lds_ptr_t;
 #define BCP_GLDS16(gsrc, lds_wave_base) __builtin_amdgcn_global_load_lds((gsrc), (bcp_lds_ptr_t)(lds_wave_base), 16, 0, 0)
 #define BCP_VM_LDS_BARRIER(N) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(N) : "memory")
+#endif
+
+// ---- an int made opaque to the optimiser (an empty asm that "rewrites" it in a scalar / vector register): what is derived from it inside a
+// loop is computed there and not hoisted in front of the loop, where it would hold registers across the whole loop body.  Value unchanged.
+// (_S: wave-uniform values only)
+#ifndef BCP_OPAQUE_S
+#if defined(__AMDGCN__)
+#define BCP_OPAQUE_S(x) asm volatile("" : "+s"(x))
+#define BCP_OPAQUE_V(x) asm volatile("" : "+v"(x))
+#else
+#define BCP_OPAQUE_S(x) ((void)0)
+#define BCP_OPAQUE_V(x) ((void)0)
+#endif
 #endif
 
 // ---- timing-only pause (s_sleep n = ~64 n clocks); the host simulator defines it away

@@ -859,8 +859,14 @@ __global__ __launch_bounds__(256) void k_c3p(const float* __restrict__ X, const 
 // global memory, the next pair's weights shared the in-order vmcnt counter with the halo prefetch: the pair after it waited for the whole
 // next-tile halo to arrive from HBM (s_waitcnt vmcnt(2) two pairs behind the fetch).  Without global loads in the tap loop the prefetch
 // has the rest of the tile to land.  Same fragment values, same MFMA order: bit-identical to WL = false (option c3d16_form = 0).
+// The persistent 32-channel-slab form (PER && NT > 1) asks for two waves per SIMD, i.e. two workgroups per CU: left alone, the allocator takes 304
+// registers for it (one workgroup per CU); held to 256 it needs 228 and no scratch.  Every other instance keeps the default bound of 1.
 #ifndef BCP_C3D_ATTR
-#define BCP_C3D_ATTR
+#if defined(__HIP__)
+#define BCP_C3D_ATTR __attribute__((amdgpu_waves_per_eu((PER && NT > 1) ? 2 : 1)))
+#else
+#define BCP_C3D_ATTR      // (the host simulator compiles the kernels as plain functions)
+#endif
 #endif
 template <int KD, int TD, int TH, int TW, int NT, bool PER, bool BW = false, int PL = 3, bool WL = false>
 __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restrict__ X, const float* __restrict__ Wp, const float* __restrict__ bias,
@@ -868,10 +874,15 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   using TL = Tile<KD, TD, TH, TW>;
   constexpr int MT = TL::MT, T = TL::T, TP = (T + 1) / 2, TPE = (TP + 1) & ~1, CT = NT * 16;
   constexpr int XPLANE = TL::HV * XSB;
-  using HF = HaloFetch<TL>;
+  // (the persistent 32-slab backward-statistics instance re-runs init() per item with a thread id the optimiser cannot see through: a fetcher
+  //  type of its own -- the row stride parameter is not used here -- keeps that call from changing how init() compiles into the other kernels)
+  using HF = HaloFetch<TL, (PER && NT > 1 && BW) ? XSB : XS>;
   using PP = Pipe<PL>;
   using frag_t = typename PP::frag;
   static_assert(!WL || (PER && NT == 1 && !BW), "LDS-resident weights: the persistent one-n-tile instances");
+  // PT: the persistent 32-channel-slab form keeps ONE STATISTICS ROW PER TILE, as the one-tile form does (same rows, same per-tile sums, same
+  // row count for the planners); its fp64 accumulators live only inside a tile's epilogue, never across a tap loop
+  constexpr bool PT = PER && NT > 1;
 
   BCP_TS(0);
   BCP_TSR(59);
@@ -887,6 +898,24 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   int voff[MT];
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) voff[mt] = TL::voff((wave * MT + mt) * 16 + b6_row<TW>(li)) * XSB + (lg & 1) * 8;
+  // PT: a lane reads tap A (lg 0-1) or tap B (lg 2-3) of a pair, and B lies 0 (the padded last pair), 1, HW - 2 or HH * HW - 2 * HW - 2 halo rows
+  // behind A: one lane base per m-tile and distance class, the pair's tap A as the read's immediate offset.  (voff[mt] + select(tA, tB) per pair
+  // is loop-invariant too, and the item loop then carries a table of MT x TP read addresses in registers: 36 of them at the 3-D tile)
+  constexpr int kTapDist[4] = {0, 1, TL::HW - 2, TL::HH * TL::HW - 2 * TL::HW - 2};
+  int vsel[PT ? 4 : 1][MT];
+  if constexpr (PT) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) vsel[c][mt] = voff[mt] + ((lg >> 1) ? kTapDist[c] * XSB : 0);
+  }
+  // PT: LDS address of the A fragment (piece I, m-tile mt) of tap pair tpq
+  auto fptr = [&](int I, int mt, int tpq) __attribute__((always_inline)) -> const frag_t* {
+    const int t0 = 2 * tpq, t1 = 2 * tpq + 1 < T ? 2 * tpq + 1 : T - 1;
+    const int tA = ((t0 / 9) * TL::HH + (t0 / 3) % 3) * TL::HW + t0 % 3, tB = ((t1 / 9) * TL::HH + (t1 / 3) % 3) * TL::HW + t1 % 3;
+    const int dl = tB - tA, c = dl == kTapDist[0] ? 0 : dl == kTapDist[1] ? 1 : dl == kTapDist[2] ? 2 : 3;
+    return reinterpret_cast<const frag_t*>(Xb + I * XPLANE + ((B6_ABLATE & 32) ? 0 : tA * XSB) + vsel[(B6_ABLATE & 32) ? 0 : c][mt]);
+  };
   HF hf;
   hf.init(cd, reinterpret_cast<float*>(smem4));
 
@@ -905,8 +934,9 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   // that list.  The halo of item it + 1 -- the NEXT TILE's first chunk after a tile's last -- travels under item it's tap pairs, so
   // the fetch latency of a tile's first halo and the epilogue stores of the previous tile overlap with MFMAs (the 16-channel
   // level has ONE chunk per tile: without this a workgroup's life is prologue + epilogue).
-  // (PER = false: one tile per workgroup -- the 32-channel-slab instances, whose persistent form needs 355 VGPRs and would drop to
-  //  one workgroup per CU: 102-109 vs 78-84 us)
+  // (PER = false: one tile per workgroup -- the 32-channel-slab instances on three bf16 planes, whose persistent form needed 355 VGPRs and
+  //  dropped to one workgroup per CU: 102-109 vs 78-84 us.  On two fp16 planes the persistent form fits two workgroups per CU once no
+  //  statistics accumulator is carried through the tap loop: PT above, option c3d32_form)
   // XCD-aware (cd.xcd): one tile per workgroup -> xcd_tile(); persistent -> each XCD (= blockIdx.x % 8 when the grid row is a multiple
   // of 8) walks ONE contiguous eighth of the tile list with its gridDim.x / 8 workgroups side by side, as k_conv3_res does
   int t_first, t_step, my_tiles;
@@ -928,7 +958,8 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   const int n_items = my_tiles * nch;
 
   // statistics: one row per (group, workgroup); rows this workgroup never reaches must read as zero
-  const bool want_stats = PER && st.partial != nullptr;
+  // (PT: one row per tile, written by the tile's epilogue -- every row of the launch is written by exactly one workgroup, nothing to zero)
+  const bool want_stats = PER && !PT && st.partial != nullptr;
   if (want_stats && (int)threadIdx.x < CT && cout0 + (int)threadIdx.x < cd.Cout) {
     for (int g = 0; g < st.G; ++g) {
       double* z = st.partial + (((long long)g * st.rows + blockIdx.x) * st.C + cout0 + threadIdx.x) * 2;
@@ -978,11 +1009,16 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   };
   auto hstash = [&]() __attribute__((always_inline)) {
     if (B6_ABLATE & 2) return;
+    // (PT: the lane's slot reaches the stores through an empty asm -- hoisted out of the item loop, the NP row addresses became NP registers
+    //  held across the tap loop; computed here they are one base and NP immediate offsets)
+    int slot = (hf.r0 * TL::HW + hf.hw) * XSB + hf.part * 4;
+    if constexpr (PT) BCP_OPAQUE_V(slot);
 #pragma unroll
     for (int u = 0; u < HF::NP; ++u)
       if (hf.act && u * HF::RPP + hf.r0 < HF::HR) {
         const float4 v = ((hvm >> u) & 1u) ? hpre[u] : make_float4(0.f, 0.f, 0.f, 0.f);
-        PP::split(v, xsc, Xb + ((u * HF::RPP + hf.r0) * TL::HW + hf.hw) * XSB + hf.part * 4, XPLANE);
+        if constexpr (PT) PP::split(v, xsc, Xb + u * HF::RPP * TL::HW * XSB + slot, XPLANE);
+        else PP::split(v, xsc, Xb + ((u * HF::RPP + hf.r0) * TL::HW + hf.hw) * XSB + hf.part * 4, XPLANE);
       }
   };
 
@@ -1021,15 +1057,31 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
   int cur_g = want_stats ? t_first / st.tiles_per_group : 0;
 #pragma unroll 1
   for (int it = 0; it < n_items; ++it) {
+    if constexpr (PT && BW) {
+      // the backward-statistics epilogue of the previous item has no room for the launch-invariant lane values of the fetch (NP row offsets)
+      // and of the fragment reads (3 * MT derived lane bases): both are rebuilt here, per item, from values the optimiser cannot see through
+      int tid = threadIdx.x;
+      BCP_OPAQUE_V(tid);
+      hf.init(cd, reinterpret_cast<float*>(smem4), tid);
+    }
     if (it > 0) {
       BCP_LDS_BARRIER();                             // every wave is done with the previous item's halo planes
       hstash();
       BCP_LDS_BARRIER();
     }
+    if constexpr (PT && BW) {
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        int vo = voff[mt];
+        BCP_OPAQUE_V(vo);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) vsel[c][mt] = vo + ((lg >> 1) ? kTapDist[c] * XSB : 0);
+      }
+    }
     const int cc = c_begin + it % nch;
     const int ccn = c_begin + (it + 1 < n_items ? (it + 1) % nch : it % nch);
 #if BCP_C3D_STREAM
-    frag_t nx[BCP_C3D_FD];                           // the next pair's first fragments (fragment stream, below)
+    frag_t nx[BCP_C3D_FD];                          // the next pair's first fragments (fragment stream, below)
 #endif
 #pragma unroll
     for (int tp = 0; tp < TPE; ++tp) {
@@ -1060,6 +1112,7 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
           const int t0n = 2 * (tp + 1), t1n = 2 * (tp + 1) + 1 < T ? 2 * (tp + 1) + 1 : T - 1;
           const int tAn = ((t0n / 9) * TL::HH + (t0n / 3) % 3) * TL::HW + t0n % 3, tBn = ((t1n / 9) * TL::HH + (t1n / 3) % 3) * TL::HW + t1n % 3;
           const int toffn = ((lg >> 1) ? tBn : tAn) * XSB;
+          // (PT: fptr() -- per-class lane bases and immediate tap offsets, see vsel)
           const bool have_nx = tp > 0;                         // (compile-time after unrolling: pair 0 of a chunk follows a barrier)
           const bool want_nx = tp + 1 < TP;
           frag_t fr[NF];
@@ -1068,6 +1121,7 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
             int mt, I;
             fidx(f, mt, I);
             if (have_nx) fr[f] = nx[f];
+            else if constexpr (PT) fr[f] = *fptr(I, mt, tp);
             else fr[f] = *reinterpret_cast<const frag_t*>(Xb + I * XPLANE + voff[mt] + ((B6_ABLATE & 32) ? 0 : toff));
           }
 #pragma unroll
@@ -1076,8 +1130,8 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
             for (int q = 0; q < MP; ++q) {
               const int g = f0 + q + FD;
               int mt, I;
-              if (g < NF) { fidx(g, mt, I); fr[g] = *reinterpret_cast<const frag_t*>(Xb + I * XPLANE + voff[mt] + ((B6_ABLATE & 32) ? 0 : toff)); }
-              else if (want_nx) { fidx(g - NF, mt, I); nx[g - NF] = *reinterpret_cast<const frag_t*>(Xb + I * XPLANE + voff[mt] + ((B6_ABLATE & 32) ? 0 : toffn)); }
+              if (g < NF) { fidx(g, mt, I); if constexpr (PT) fr[g] = *fptr(I, mt, tp); else fr[g] = *reinterpret_cast<const frag_t*>(Xb + I * XPLANE + voff[mt] + ((B6_ABLATE & 32) ? 0 : toff)); }
+              else if (want_nx) { fidx(g - NF, mt, I); if constexpr (PT) nx[g - NF] = *fptr(I, mt, tp + 1); else nx[g - NF] = *reinterpret_cast<const frag_t*>(Xb + I * XPLANE + voff[mt] + ((B6_ABLATE & 32) ? 0 : toffn)); }
             }
             __builtin_amdgcn_sched_barrier(0);
             int mt0, I;
@@ -1124,12 +1178,34 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
         BCP_TSR(62);
         return;
       }
-      if (want_stats && tl / st.tiles_per_group != cur_g) {
-        BCP_LDS_BARRIER();
-        stats_flush_t<NT>(s1, s2, Ss, st.partial + ((long long)cur_g * st.rows + blockIdx.x) * st.C * 2, cout0, cd.Cout);
-        cur_g = tl / st.tiles_per_group;
+      if constexpr (PT) {
+        // the one-tile epilogue (b6_epilogue) on tile tl: local accumulators, row tl % tiles_per_group of group tl / tiles_per_group; the
+        // barrier stands in front of the scratch use (the scratch aliases no halo plane, and the next item's halo waits in registers until the
+        // loop head).  Everything the epilogue derives from the lane and the launch constants -- bias values, row offsets, edge tests -- is
+        // loop-invariant here, and hoisted out of the item loop it would sit in registers across every tap loop: the wave index and the
+        // slab origin reach it through an empty asm, so it is computed where it is used
+        int wv = __builtin_amdgcn_readfirstlane(wave), co0 = cout0;
+        BCP_OPAQUE_S(wv);
+        BCP_OPAQUE_S(co0);
+        const int gg = st.partial ? tl / st.tiles_per_group : 0;
+        double s1[NT][4], s2[NT][4];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { s1[nt][r] = 0.0; s2[nt][r] = 0.0; }
+        b6_store_tile<TL, TD, TH, TW, NT, TL::MT, BW>(acc, Y, bias, cd, n, d0, h0, w0, co0, accumulate, st.partial != nullptr, s1, s2, wv, &st, gg, osc);
+        if (st.partial) {
+          BCP_LDS_BARRIER();
+          stats_flush_t<NT>(s1, s2, Ss, st.partial + ((long long)gg * st.rows + tl % st.tiles_per_group) * st.C * 2, co0, cd.Cout);
+        }
+      } else {
+        if (want_stats && tl / st.tiles_per_group != cur_g) {
+          BCP_LDS_BARRIER();
+          stats_flush_t<NT>(s1, s2, Ss, st.partial + ((long long)cur_g * st.rows + blockIdx.x) * st.C * 2, cout0, cd.Cout);
+          cur_g = tl / st.tiles_per_group;
+        }
+        b6_store_tile<TL, TD, TH, TW, NT, TL::MT, BW>(acc, Y, bias, cd, n, d0, h0, w0, cout0, accumulate, want_stats, s1, s2, -1, &st, cur_g, osc);
       }
-      b6_store_tile<TL, TD, TH, TW, NT, TL::MT, BW>(acc, Y, bias, cd, n, d0, h0, w0, cout0, accumulate, want_stats, s1, s2, -1, &st, cur_g, osc);
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
@@ -1657,6 +1733,14 @@ constexpr bool b6_has_f16() {
                      (KD == 3 && TD * TH * TW == 64 && NT == 4));        // k_c3p (64-voxel x 64-channel pipeline, 4x4x4 / 2x8x4 bricks; not its register-staged twins)
 }
 
+// tile configurations whose 32-channel-slab two-plane instance of k_c3d also exists in the persistent one-row-per-tile form (option
+// c3d32_form): the 3-D 4x8x8 tile.  (The 2-D 16x16 instances stay one tile per workgroup.)
+template <int KD, int TD, int TH, int TW, int NT, int SP>
+constexpr bool b6_has_per32() { return SP == 1 && KD == 3 && TD == 4 && TH == 8 && TW == 8 && NT == 2; }
+// ... and whether its backward-statistics instance takes that form too (it passes the same register gate once the launch-invariant lane values
+// are rebuilt per item: DESIGN.md section 3a)
+static constexpr bool b6_per32_bw = true;
+
 // dynamic LDS of k_c3p: two halo buffers, three weight slots, statistics scratch
 template <class TL, int PL = 3>
 static constexpr size_t kC3pLds = (size_t)2 * PL * TL::HV * XSB * 2 + (size_t)3 * PL * 64 * 32 * 2 + (size_t)4 * 32 * 2 * sizeof(double);
@@ -1732,13 +1816,17 @@ static int b6_launch(const float* X, const float* Wp, const float* bias, float* 
   }
   if (direct) {
     // persistent grid (16-channel slabs): tiles dealt round-robin to P workgroups (two per CU), balanced: every workgroup gets
-    // cdiv(tiles, slots) tiles; 32-channel slabs: one tile per workgroup (register budget, see k_c3d)
+    // cdiv(tiles, slots) tiles; 32-channel slabs: one tile per workgroup (register budget, see k_c3d) except PT below
     constexpr bool PER = NT == 1;
+    // PT (option c3d32_form): the 3-D 32-channel slabs on two fp16 planes as persistent workgroups too -- the same balanced deal and XCD walk,
+    // but still ONE STATISTICS ROW PER TILE, so the row count below (and with it every planner's answer) does not depend on the form
+    bool PT = false;
+    if constexpr (b6_has_per32<KD, TD, TH, TW, NT, SP>()) PT = use_f16 && sk == 1 && options().c3d32_form != 0 && (!bw || b6_per32_bw);
     const int slots = 512 / (gy * sk) > 0 ? 512 / (gy * sk) : 1;
-    const int per = PER ? cdiv(gx, slots) : 1;
+    const int per = (PER || PT) ? cdiv(gx, slots) : 1;
     int P = cdiv(gx, per);
-    if (PER && (cd.xcd & 2) && P >= 8) P = (P + 7) & ~7;                                           // the XCD-aware walk needs whole rounds of the 8 XCDs
-    if (PER && options().conv3_p > 0 && options().conv3_p < P) P = options().conv3_p;      // tests: few workgroups, many tiles each
+    if ((PER || PT) && (cd.xcd & 2) && P >= 8) P = (P + 7) & ~7;                                           // the XCD-aware walk needs whole rounds of the 8 XCDs
+    if ((PER || PT) && options().conv3_p > 0 && options().conv3_p < P) P = options().conv3_p;      // tests: few workgroups, many tiles each
     StatsArg sd{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
     if (sk == 1 && G > 0 && gx % G == 0) { sd.rows = PER ? P : gx / G; sd.tiles_per_group = gx / G; sd.partial = stat_partial; }
     if (bw) { sd.by = bw->y; sd.bstats = bw->stats; sd.bact = bw->act; }
@@ -1753,6 +1841,14 @@ static int b6_launch(const float* X, const float* Wp, const float* bias, float* 
         kd = k_c3d<KD, TD, TH, TW, NT, PER, false, 2>;
         if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>() && !PER) {
           if (bw) kd = k_c3d<KD, TD, TH, TW, NT, PER, true, 2>;
+        }
+        if constexpr (b6_has_per32<KD, TD, TH, TW, NT, SP>()) {
+          if (PT) {
+            kd = k_c3d<KD, TD, TH, TW, NT, true, false, 2>;
+            if constexpr (b6_per32_bw && b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
+              if (bw) kd = k_c3d<KD, TD, TH, TW, NT, true, true, 2>;
+            }
+          }
         }
         if constexpr (PER) {
           // the weight fragments of the one cin chunk in the LDS (option c3d16_form): 14 pairs x 2 planes x 1 KB at the 3-D tile,

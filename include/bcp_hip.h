@@ -50,7 +50,9 @@ const char* bcp_last_error(void);
  * conv3_b6*, wgrad_b6*: which shapes run on the bf16 matrix pipe and with which tiles; norm_slabs, conv3_xcd; round 6: norm_fuse_fin, norm_own,
  * wgrad_reduce_flat, gemm_pipe (the statistics GEMMs' row-block walk prefetches the next block), cc_fuse_select / cc_border_dedupe (the largest-CC chain's
  * fused selection and wave-level pair exchange), c3d16_form (the persistent 16-output-channel conv on fp16 planes: 1 = its weight fragments held
- * in the LDS, the default; 0 = streamed from global memory one tap pair ahead, bit-identical), the measurement switches gemm_walk, gemm_stat_r, norm_apply_cap, norm_apply_vec, cc_count_tile, and the MEASUREMENT-ONLY whatif bits that leave launches out -- wrong results, for pricing a change); value = decimal integer(s), comma separated for the array-valued ones; "" restores the default.
+ * in the LDS, the default; 0 = streamed from global memory one tap pair ahead, bit-identical), c3d32_form (the 3-D 32-channel-slab conv on fp16
+ * planes: 1 = persistent workgroups that fetch the next tile's halo under the current tile, the default; 0 = one tile per workgroup, bit-identical, same
+ * statistics rows), the measurement switches gemm_walk, gemm_stat_r, norm_apply_cap, norm_apply_vec, cc_count_tile, and the MEASUREMENT-ONLY whatif bits that leave launches out -- wrong results, for pricing a change); value = decimal integer(s), comma separated for the array-valued ones; "" restores the default.
  * HOST strings.  NOT thread-safe and not per-stream: ONE Options struct per process, read by every launch on every stream and
  * device.  Set options before work is enqueued, never concurrently with launches from another thread (the launch entry points
  * themselves are re-entrant across streams / devices as long as the options stay put). */
