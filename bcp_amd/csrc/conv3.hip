@@ -1310,67 +1310,6 @@ __global__ __launch_bounds__(256) void k_conv3_c1_wgrad(const float* __restrict_
 // host-side dispatch
 // ------------------------------------------------------------------------------------------------
 
-static int split_k(long long blocks, int nch) {   // deep levels: too few tiles to fill 256 CUs -> split the cin chunks
-  const int f = options().splitk;
-  if (f >= 1 && f <= 4 && f <= nch) return f;
-  if (blocks > 256 || nch < 4) return 1;
-  int sk = nch / 2;
-  if (sk > 4) sk = 4;
-  return sk;
-}
-
-template <int KD, int TD, int TH, int TW, int NT, int WT>
-static int launch_fwd(const float* X, const float* Wp, const float* bias, float* Y, ConvDims cd, int accumulate, float* ws,
-                      double* stat_partial, int G, bool dry, hipStream_t s) {
-  using TL = Tile<KD, TD, TH, TW>;
-  constexpr int S = TL::T / WT, NBUF = S > 1 ? 2 : 1;
-  const size_t lds = (size_t)(TL::HV * XS + NBUF * WT * 4 * NT * 16 * 4) * sizeof(float) + 4 * NT * 16 * 2 * sizeof(double);
-  cd.tiles_d = cdiv(cd.D, TD); cd.tiles_h = cdiv(cd.H, TH); cd.tiles_w = cdiv(cd.W, TW);
-  auto kfn = k_conv3_mfma<KD, TD, TH, TW, NT, WT>;
-  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int gx = cd.N * cd.tiles_d * cd.tiles_h * cd.tiles_w, gy = cd.Cout16 / (NT * 16);
-  const int sk = ws ? split_k((long long)gx * gy, cd.Cin16 / 16) : 1;
-  StatsArg st{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
-  if (sk == 1 && G > 0 && gx % G == 0) { st.rows = gx / G; st.tiles_per_group = gx / G; st.partial = stat_partial; }
-  if (dry) return sk == 1 && G > 0 && gx % G == 0 ? gx / G : 0;
-  if (sk == 1) {
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, 1), dim3(256), lds, s, X, Wp, bias, Y, cd, accumulate, st);
-  } else {
-    const long long n = (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout;
-    StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, sk), dim3(256), lds, s, X, Wp, (const float*)nullptr, ws, cd, 0, none);
-    hipLaunchKernelGGL(k_sum_slabs, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, sk, n, cd.Cout, bias, Y, accumulate);
-  }
-  return st.partial ? st.rows : 0;
-}
-
-template <int KD, int TD, int TH, int TW, int NT>
-static int launch_res(const float* X, const float* Wp, const float* bias, float* Y, ConvDims cd, int accumulate,
-                      double* stat_partial, int G, bool dry, hipStream_t s) {
-  using TL = Tile<KD, TD, TH, TW>;
-  const int nch = cd.Cin16 / 16;                        // resident chunks per workgroup
-  const size_t lds = ((size_t)nch * TL::T * 4 * NT * 16 * 4 + (size_t)TL::HV * XS) * sizeof(float) + 4 * NT * 16 * 2 * sizeof(double);
-  cd.tiles_d = cdiv(cd.D, TD); cd.tiles_h = cdiv(cd.H, TH); cd.tiles_w = cdiv(cd.W, TW);
-  const int tiles = cd.N * cd.tiles_d * cd.tiles_h * cd.tiles_w;
-  const int slabs = cd.Cout16 / (NT * 16);
-  const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-  int P = (256 * (per_cu > 3 ? 3 : per_cu)) / slabs;    // persistent workgroups per slab
-  if (per_cu > 2) P = 512 / slabs;
-  const Options& o = options();
-  if (o.res_pcu >= 1 && o.res_pcu <= 4 && o.res_pcu <= per_cu) P = 256 * o.res_pcu / slabs;
-  if (o.conv3_p > 0 && o.conv3_p < P) P = o.conv3_p;    // tests: force multi-tile loops
-  if (P < 1) P = 1;
-  if (P > tiles) P = tiles;
-  StatsArg st{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
-  const bool stats_ok = G > 0 && tiles % G == 0;
-  if (dry) return stats_ok ? P : 0;
-  if (stats_ok && stat_partial) { st.partial = stat_partial; st.rows = P; st.tiles_per_group = tiles / G; }   // (rows of unvisited groups are zeroed by the kernel itself)
-  auto kfn = k_conv3_res<KD, TD, TH, TW, NT>;
-  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(kfn, dim3(P, slabs, 1), dim3(256), lds, s, X, Wp, bias, Y, cd, tiles, accumulate, st, 1);
-  return st.partial ? P : 0;
-}
-
 template <int KD, int TD, int TH, int TW, int NT>
 static int launch_wgrad(const float* X, const float* dY, float* partial, ConvDims cd, int groups, hipStream_t s) {
   using TL = Tile<KD, TD, TH, TW>;
@@ -1428,8 +1367,8 @@ static Cfg choose_cfg(int KD, int N, int D, int H, int W, int Cout16, bool for_w
 // conv3b.hip / conv3bw.hip: fp32 numerics on the bf16 matrix pipe (three-piece operands)
 int b6_wgrad(const float* x, const float* dy, float* partial, float* dw, int accumulate, const ConvDims& cd, int KD, hipStream_t s);
 size_t b6_wgrad_workspace_bytes(const ConvDims& cd, int KD);
-int b6_fwd(const float* x, const float* wp, const float* bias, float* y, const ConvDims& cd, int KD, int accumulate, void* workspace,
-           double* stat_partial, int G, bool dry, hipStream_t s, bool* handled, int* raw_sk = nullptr, const BwdStatsIn* bw = nullptr);
+bool b6_route(Conv3Route& r, int KD, Conv3Mode mode, int G, bool has_workspace, bool has_amax);
+Conv3Kernel b6_kernel(const Conv3Route& r);
 
 }  // namespace bcp
 
@@ -1484,17 +1423,6 @@ extern "C" int bcp_conv3_pack_many(const void* descs_dev, int n, void* stream) {
   return BCP_OK;
 }
 
-#define BCP_FWD_CASE(KD_, TD_, TH_, TW_, NT_, WT_)                                                             \
-  if (c.KD == KD_ && c.TD == TD_ && c.TH == TH_ && c.TW == TW_ && c.NT == NT_) {                               \
-    rows = launch_fwd<KD_, TD_, TH_, TW_, NT_, WT_>(x, wp, bias, y, cd, accumulate, (float*)workspace, stat_partial, G, dry, (hipStream_t)stream); \
-    done = true;                                                                                               \
-  }
-#define BCP_RES_CASE(KD_, TD_, TH_, TW_, NT_)                                                                  \
-  if (r.KD == KD_ && r.TD == TD_ && r.TH == TH_ && r.TW == TW_ && r.NT == NT_) {                               \
-    rows = launch_res<KD_, TD_, TH_, TW_, NT_>(x, wp, bias, y, cd, accumulate, stat_partial, G, dry, (hipStream_t)stream); \
-    done = true;                                                                                               \
-  }
-
 // resident-weight variant: tile by problem size, widest channel slab whose weights + one halo fit in LDS
 static bool choose_res(Cfg& r, int KD, int N, int D, int H, int W, int Cin16, int Cout16) {
   r.KD = KD;
@@ -1534,57 +1462,170 @@ extern "C" size_t bcp_conv3_fwd_workspace_bytes(int N, int D, int H, int W, int 
   return n <= options().conv3_sk_elems ? (size_t)(8 * n * sizeof(float)) : 0;
 }
 
-// shared by the launch and by the statistics-rows query: returns the number of partial rows per group the chosen kernel
-// writes (0: this shape does not support fused statistics, e.g. split-K), or a negative error
-namespace bcp { int b6_last_planes(); }
-// which SECTION of the packed weight the last real (non-dry) forward / dgrad launch of this thread read: 1 = the fp32 pack (conv3.hip kernels),
+// ---- the fp32 kernels' instances: every one is named here once; nullptr: no such instance
+static constexpr int tile_key(int KD, int TD, int TH, int TW) { return ((KD * 32 + TD) * 32 + TH) * 32 + TW; }
+
+template <int KD, int TD, int TH, int TW>
+static Conv3KernelA mfma_instance(int NT) {           // taps per weight stage: fewer as the slab widens
+  if (NT == 1) return k_conv3_mfma<KD, TD, TH, TW, 1, KD == 3 ? 27 : 9>;
+  if (NT == 2) return k_conv3_mfma<KD, TD, TH, TW, 2, 9>;
+  if (NT == 4) return k_conv3_mfma<KD, TD, TH, TW, 4, 3>;
+  return nullptr;
+}
+static int mfma_stage_taps(int KD, int NT) { return NT == 1 ? (KD == 3 ? 27 : 9) : (NT == 2 ? 9 : 3); }
+
+template <int KD, int TD, int TH, int TW, bool NT4 = true>
+static Conv3KernelRes res_instance(int NT) {
+  if (NT == 1) return k_conv3_res<KD, TD, TH, TW, 1>;
+  if (NT == 2) return k_conv3_res<KD, TD, TH, TW, 2>;
+  if constexpr (NT4) { if (NT == 4) return k_conv3_res<KD, TD, TH, TW, 4>; }
+  return nullptr;
+}
+
+static Conv3Kernel fp32_kernel(const Conv3Route& r) {
+  Conv3Kernel k;
+  k.sum = k_sum_slabs;
+  if (r.family == Conv3Family::res) {
+    switch (tile_key(r.KD, r.TD, r.TH, r.TW)) {
+      case tile_key(3, 4, 4, 16): k.res = res_instance<3, 4, 4, 16, false>(r.NT); break;
+      case tile_key(3, 4, 4, 8): k.res = res_instance<3, 4, 4, 8>(r.NT); break;
+      case tile_key(3, 4, 4, 4): k.res = res_instance<3, 4, 4, 4>(r.NT); break;
+      case tile_key(1, 1, 16, 16): k.res = res_instance<1, 1, 16, 16>(r.NT); break;
+      case tile_key(1, 1, 8, 8): k.res = res_instance<1, 1, 8, 8>(r.NT); break;
+    }
+  } else if (r.family == Conv3Family::mfma) {
+    switch (tile_key(r.KD, r.TD, r.TH, r.TW)) {
+      case tile_key(3, 4, 4, 16): k.a = mfma_instance<3, 4, 4, 16>(r.NT); break;
+      case tile_key(3, 4, 8, 8): k.a = mfma_instance<3, 4, 8, 8>(r.NT); break;
+      case tile_key(3, 4, 4, 4): k.a = mfma_instance<3, 4, 4, 4>(r.NT); break;
+      case tile_key(3, 2, 8, 4): k.a = mfma_instance<3, 2, 8, 4>(r.NT); break;
+      case tile_key(3, 2, 16, 2): k.a = mfma_instance<3, 2, 16, 2>(r.NT); break;
+      case tile_key(3, 8, 8, 1): k.a = mfma_instance<3, 8, 8, 1>(r.NT); break;
+      case tile_key(1, 1, 16, 16): k.a = mfma_instance<1, 1, 16, 16>(r.NT); break;
+      case tile_key(1, 1, 8, 8): k.a = mfma_instance<1, 1, 8, 8>(r.NT); break;
+    }
+  }
+  return k;
+}
+
+// ---- the decision.  Statistics rows: the number of partial rows per group the chosen kernel writes (0: this shape does not support fused
+// statistics, e.g. split-K -- not served in that mode)
+static void route_tile(Conv3Route& r, Conv3Family family, const Cfg& c) {
+  r.family = family;
+  r.KD = c.KD; r.TD = c.TD; r.TH = c.TH; r.TW = c.TW; r.NT = c.NT;
+  r.cd.tiles_d = cdiv(r.cd.D, c.TD); r.cd.tiles_h = cdiv(r.cd.H, c.TH); r.cd.tiles_w = cdiv(r.cd.W, c.TW);
+  r.tiles = r.cd.N * r.cd.tiles_d * r.cd.tiles_h * r.cd.tiles_w;
+}
+
+Conv3Route bcp::conv3_route(const ConvDims& dims, int KD, Conv3Mode mode, int groups, bool has_workspace, bool has_amax) {
+  const Options& o = options();
+  const int G = mode == Conv3Mode::fwd_stats || mode == Conv3Mode::bwd_stats ? groups : 0;
+  Conv3Route r;
+  r.cd = dims;
+  r.cd.xamax = r.cd.yamax = nullptr;
+  r.groups = G > 0 ? G : 1;
+  if (mode == Conv3Mode::raw && (!has_workspace || (long long)dims.N * dims.D * dims.H * dims.W * dims.Cout > o.conv3_sk_elems))
+    return r;                                         // the slab buffer is sized like bcp_conv3_fwd_workspace_bytes: deep levels only
+  if (b6_route(r, KD, mode, G, has_workspace, has_amax)) {
+    r.section = r.planes == 2 ? 4 : 2;
+    r.sum_slabs = r.sk > 1 && mode != Conv3Mode::raw;
+    return r;
+  }
+  if (mode == Conv3Mode::raw || mode == Conv3Mode::bwd_stats) return r;      // bf16-pipe kernels only
+  const ConvDims& cd = r.cd;
+  const int PD = KD == 3 ? 1 : 0, T = KD * 9;
+  r.section = 1;
+  Cfg c;
+  if (choose_res(c, KD, cd.N, cd.D, cd.H, cd.W, cd.Cin16, cd.Cout16)) route_tile(r, Conv3Family::res, c);
+  if (r.family == Conv3Family::res && fp32_kernel(r).res) {
+    const int HV = (c.TD + 2 * PD) * (c.TH + 2) * (c.TW + 2), nch = cd.Cin16 / 16;      // resident chunks per workgroup
+    r.lds = ((size_t)nch * T * 4 * c.NT * 16 * 4 + (size_t)HV * XS) * sizeof(float) + 4 * c.NT * 16 * 2 * sizeof(double);
+    const int slabs = cd.Cout16 / (c.NT * 16);
+    const int per_cu = (int)((160 * 1024) / r.lds) < 1 ? 1 : (int)((160 * 1024) / r.lds);
+    int P = (256 * (per_cu > 3 ? 3 : per_cu)) / slabs;    // persistent workgroups per slab
+    if (per_cu > 2) P = 512 / slabs;
+    if (o.res_pcu >= 1 && o.res_pcu <= 4 && o.res_pcu <= per_cu) P = 256 * o.res_pcu / slabs;
+    if (o.conv3_p > 0 && o.conv3_p < P) P = o.conv3_p;    // tests: force multi-tile loops
+    if (P < 1) P = 1;
+    if (P > r.tiles) P = r.tiles;
+    r.gx = P; r.gy = slabs;
+    if (G > 0 && r.tiles % G == 0) { r.rows = P; r.tiles_per_group = r.tiles / G; }   // (rows of unvisited groups are zeroed by the kernel itself)
+  } else {
+    c = choose_cfg(KD, cd.N, cd.D, cd.H, cd.W, cd.Cout16);
+    route_tile(r, Conv3Family::mfma, c);
+    if (!fp32_kernel(r).a) return r;                  // (a forced conv3_cfg without an instance: the caller reports r's tile)
+    r.SP = mfma_stage_taps(KD, c.NT);
+    const int HV = (c.TD + 2 * PD) * (c.TH + 2) * (c.TW + 2), NBUF = T / r.SP > 1 ? 2 : 1;
+    r.lds = (size_t)(HV * XS + NBUF * r.SP * 4 * c.NT * 16 * 4) * sizeof(float) + 4 * c.NT * 16 * 2 * sizeof(double);
+    r.gx = r.tiles; r.gy = cd.Cout16 / (c.NT * 16);
+    r.sk = has_workspace ? conv3_split_k((long long)r.gx * r.gy, cd.Cin16 / 16, false) : 1;
+    r.sum_slabs = r.sk > 1;
+    if (r.sk == 1 && G > 0 && r.tiles % G == 0) { r.rows = r.tiles / G; r.tiles_per_group = r.tiles / G; }
+  }
+  r.served = mode == Conv3Mode::plain || r.rows > 0;
+  return r;
+}
+
+// ---- the launch: executes a record, decides nothing
+// which SECTION of the packed weight the last forward / dgrad launch of this thread read: 1 = the fp32 pack (conv3.hip kernels),
 // 2 = the three bf16 planes, 4 = the two fp16 planes (conv3b.hip).  The host learns from it which sections a layer's packs must hold
-// (bcp_conv3_last_section; networks/_hipnet.py)
+// (bcp_conv3_last_section; networks/_hipnet.py).  Set by conv3_launch alone.
 static thread_local int g_last_section = 0;
 
-static int conv3_fwd_impl(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin, int Cout,
-                          int KD, int accumulate, void* workspace, double* stat_partial, int G, bool dry, void* stream,
-                          const float* x_amax = nullptr) {
+static int conv3_launch(const Conv3Route& r, const float* x, const float* wp, const float* bias, float* y, float* ws, double* stat_partial,
+                        const BwdStatsIn* bw, const float* x_amax, int accumulate, hipStream_t s) {
+  const Conv3Kernel k = r.family == Conv3Family::mfma || r.family == Conv3Family::res ? fp32_kernel(r) : b6_kernel(r);
+  BCP_REQUIRE(r.served && k.fn(), "conv3_launch: no kernel instance for family %d KD=%d tile=%dx%dx%d NT=%d planes=%d", (int)r.family, r.KD, r.TD,
+              r.TH, r.TW, r.NT, r.planes);
+  BCP_REQUIRE(!r.sum_slabs || ws, "conv3_launch: a split-K route without a workspace");
+  ConvDims cd = r.cd;
+  cd.xamax = r.planes == 2 ? x_amax : nullptr;
+  StatsArg st{nullptr, 0, 1, cd.Cout, r.groups};
+  if (r.rows > 0) { st.partial = stat_partial; st.rows = r.rows; st.tiles_per_group = r.tiles_per_group; }
+  if (r.bw) { st.by = bw->y; st.bstats = bw->stats; st.bact = bw->act; }
+  // split-K (sk > 1): the launch writes sk partial slabs, no bias -- into the workspace, where one slab-sum launch folds them into y (with
+  // the bias), or in raw mode into y itself, the caller's float[sk][N*D*H*W*Cout], where they stay
+  const bool partial = r.sk > 1;
+  const float* kbias = partial ? nullptr : bias;
+  float* out = r.sum_slabs ? ws : y;
+  const int acc = partial ? 0 : accumulate;
+  if (r.lds > 48 * 1024) hipFuncSetAttribute(k.fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.lds);
+  const dim3 grid(r.gx, r.gy, r.sk);
+  if (k.a) hipLaunchKernelGGL(k.a, grid, dim3(256), r.lds, s, x, wp, kbias, out, cd, acc, st);
+  else if (k.t) hipLaunchKernelGGL(k.t, grid, dim3(256), r.lds, s, x, wp, kbias, out, cd, r.tiles, acc, st);
+  else hipLaunchKernelGGL(k.res, grid, dim3(256), r.lds, s, x, wp, kbias, out, cd, r.tiles, acc, st, 1);
+  if (r.sum_slabs) {
+    const long long n = (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout;
+    hipLaunchKernelGGL(k.sum, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, r.sk, n, cd.Cout, bias, y, accumulate);
+  }
+  g_last_section = r.section;
+  return BCP_OK;
+}
+
+// ---- entry points: check the arguments, compute the route, compare it with what the caller promised, launch
+static bool conv3_shape_ok(int N, int D, int H, int W, int Cin, int KD) {
+  return (KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0 && Cin % 4 == 0 && Cin >= 4;
+}
+static int conv3_check_args(const char* fn, bool pointers, bool aligned, int N, int D, int H, int W, int Cin, int KD, int groups) {
+  BCP_REQUIRE(pointers, "%s: null pointer", fn);
+  BCP_REQUIRE((KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0 && groups >= 1, "%s: bad extents", fn);
+  BCP_REQUIRE(KD == 3 || D == 1, "%s: KD=1 needs D=1", fn);
+  BCP_REQUIRE(Cin % 4 == 0 && Cin >= 4, "%s: Cin=%d must be a multiple of 4 (Cin=1 has its own entry point)", fn, Cin);
+  BCP_REQUIRE(aligned, "%s: the tensors and the packed weight must be 16-B aligned", fn);
+  return BCP_OK;
+}
+static Conv3Route conv3_route(int N, int D, int H, int W, int Cin, int Cout, int KD, Conv3Mode mode, int groups, bool has_workspace, bool has_amax) {
   ConvDims cd;
   fill_dims(cd, N, D, H, W, Cin, Cout);
-  cd.xamax = x_amax;
-  bool done = false;
-  int rows = 0;
-  Cfg r;
-  rows = b6_fwd(x, wp, bias, y, cd, KD, accumulate, workspace, stat_partial, G, dry, (hipStream_t)stream, &done);
-  if (!dry) g_last_section = done ? (bcp::b6_last_planes() == 2 ? 4 : 2) : 1;
-  if (done) return rows;
-  if (choose_res(r, KD, N, D, H, W, cd.Cin16, cd.Cout16)) {
-    BCP_RES_CASE(3, 4, 4, 16, 1) BCP_RES_CASE(3, 4, 4, 16, 2)
-    BCP_RES_CASE(3, 4, 4, 8, 1) BCP_RES_CASE(3, 4, 4, 8, 2) BCP_RES_CASE(3, 4, 4, 8, 4)
-    BCP_RES_CASE(3, 4, 4, 4, 1) BCP_RES_CASE(3, 4, 4, 4, 2) BCP_RES_CASE(3, 4, 4, 4, 4)
-    BCP_RES_CASE(1, 1, 16, 16, 1) BCP_RES_CASE(1, 1, 16, 16, 2) BCP_RES_CASE(1, 1, 16, 16, 4)
-    BCP_RES_CASE(1, 1, 8, 8, 1) BCP_RES_CASE(1, 1, 8, 8, 2) BCP_RES_CASE(1, 1, 8, 8, 4)
-  }
-  if (!done) {
-    const Cfg c = choose_cfg(KD, N, D, H, W, cd.Cout16);
-    BCP_FWD_CASE(3, 4, 4, 16, 1, 27) BCP_FWD_CASE(3, 4, 4, 16, 2, 9) BCP_FWD_CASE(3, 4, 4, 16, 4, 3)
-    BCP_FWD_CASE(3, 4, 8, 8, 1, 27) BCP_FWD_CASE(3, 4, 8, 8, 2, 9) BCP_FWD_CASE(3, 4, 8, 8, 4, 3)
-    BCP_FWD_CASE(3, 4, 4, 4, 1, 27) BCP_FWD_CASE(3, 4, 4, 4, 2, 9) BCP_FWD_CASE(3, 4, 4, 4, 4, 3)
-    BCP_FWD_CASE(3, 2, 8, 4, 1, 27) BCP_FWD_CASE(3, 2, 8, 4, 2, 9) BCP_FWD_CASE(3, 2, 8, 4, 4, 3)
-    BCP_FWD_CASE(3, 2, 16, 2, 1, 27) BCP_FWD_CASE(3, 2, 16, 2, 2, 9) BCP_FWD_CASE(3, 2, 16, 2, 4, 3)
-    BCP_FWD_CASE(3, 8, 8, 1, 1, 27) BCP_FWD_CASE(3, 8, 8, 1, 2, 9) BCP_FWD_CASE(3, 8, 8, 1, 4, 3)
-    BCP_FWD_CASE(1, 1, 16, 16, 1, 9) BCP_FWD_CASE(1, 1, 16, 16, 2, 9) BCP_FWD_CASE(1, 1, 16, 16, 4, 3)
-    BCP_FWD_CASE(1, 1, 8, 8, 1, 9) BCP_FWD_CASE(1, 1, 8, 8, 2, 9) BCP_FWD_CASE(1, 1, 8, 8, 4, 3)
-    BCP_REQUIRE(done, "bcp_conv3_fwd: no kernel instance for KD=%d tile=%dx%dx%d NT=%d", c.KD, c.TD, c.TH, c.TW, c.NT);
-  }
-  return rows;
+  return conv3_route(cd, KD, mode, groups, has_workspace, has_amax);
 }
 
 extern "C" int bcp_conv3_fwd(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
                              int Cout, int KD, int accumulate, void* workspace, const float* x_amax_or_null, void* stream) {
-  BCP_REQUIRE(x && wp && y, "bcp_conv3_fwd: null pointer");
-  BCP_REQUIRE((KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0, "bcp_conv3_fwd: bad extents");
-  BCP_REQUIRE(KD == 3 || D == 1, "bcp_conv3_fwd: KD=1 needs D=1");
-  BCP_REQUIRE(Cin % 4 == 0 && Cin >= 4, "bcp_conv3_fwd: Cin=%d must be a multiple of 4 (Cin=1 has its own entry point)", Cin);
-  BCP_REQUIRE(aligned16(x) && aligned16(wp), "bcp_conv3_fwd: x / wp must be 16-B aligned");
-  const int rc = conv3_fwd_impl(x, wp, bias, y, N, D, H, W, Cin, Cout, KD, accumulate, workspace, nullptr, 0, false, stream, x_amax_or_null);
-  if (rc < 0) return rc;
+  if (const int rc = conv3_check_args("bcp_conv3_fwd", x && wp && y, aligned16(x) && aligned16(wp), N, D, H, W, Cin, KD, 1)) return rc;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::plain, 0, workspace != nullptr, x_amax_or_null != nullptr);
+  BCP_REQUIRE(r.served, "bcp_conv3_fwd: no kernel instance for KD=%d tile=%dx%dx%d NT=%d", r.KD, r.TD, r.TH, r.TW, r.NT);
+  if (const int rc = conv3_launch(r, x, wp, bias, y, (float*)workspace, nullptr, nullptr, x_amax_or_null, accumulate, (hipStream_t)stream)) return rc;
   BCP_CHECK_LAUNCH("bcp_conv3_fwd");
   return BCP_OK;
 }
@@ -1594,11 +1635,20 @@ extern "C" int bcp_conv3_fwd(const float* x, const float* wp, const float* bias,
 // stat_partial[groups][rows][Cout][2] doubles; rows == 0 means "not available for this shape": run bcp_conv3_fwd and
 // let bcp_norm_fwd compute its own statistics.
 extern "C" int bcp_conv3_stat_rows(int N, int D, int H, int W, int Cin, int Cout, int KD, int groups, int has_workspace) {
-  if (Cin % 4 || Cin < 4 || groups < 1) return 0;
-  static float dummy;
-  const int rc = conv3_fwd_impl(nullptr, nullptr, nullptr, nullptr, N, D, H, W, Cin, Cout, KD, 0, has_workspace ? &dummy : nullptr, nullptr,
-                                groups, true, nullptr);
-  return rc < 0 ? 0 : rc;
+  if (!conv3_shape_ok(N, D, H, W, Cin, KD) || groups < 1) return 0;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::fwd_stats, groups, has_workspace != 0, false);
+  return r.served ? r.rows : 0;
+}
+
+extern "C" int bcp_conv3_fwd_stats(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
+                                   int Cout, int KD, void* workspace, double* stat_partial, int groups, const float* x_amax_or_null,
+                                   void* stream) {
+  if (const int rc = conv3_check_args("bcp_conv3_fwd_stats", x && wp && y && stat_partial, aligned16(x) && aligned16(wp), N, D, H, W, Cin, KD, groups)) return rc;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::fwd_stats, groups, workspace != nullptr, x_amax_or_null != nullptr);
+  BCP_REQUIRE(r.served && r.rows > 0, "bcp_conv3_fwd_stats: fused statistics unavailable for this shape (check bcp_conv3_stat_rows first)");
+  if (const int rc = conv3_launch(r, x, wp, bias, y, (float*)workspace, stat_partial, nullptr, x_amax_or_null, 0, (hipStream_t)stream)) return rc;
+  BCP_CHECK_LAUNCH("bcp_conv3_fwd_stats");
+  return BCP_OK;
 }
 
 // which matrix pipe serves bcp_conv3_fwd / _fwd_stats for this shape under the current options: 0 = v_mfma_f32_16x16x4_f32 (fp32
@@ -1606,28 +1656,20 @@ extern "C" int bcp_conv3_stat_rows(int N, int D, int H, int W, int Cin, int Cout
 // For the measurement record (bench.py prices the two against different peaks); no launch.
 extern "C" size_t bcp_conv3_fwd_path(int N, int D, int H, int W, int Cin, int Cout, int KD) {
   if (Cin % 4 || Cin < 4) return 0;
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  bool handled = false;
-  static float dummy;
-  b6_fwd(nullptr, nullptr, nullptr, nullptr, cd, KD, 0, &dummy, nullptr, 0, true, nullptr, &handled);
-  return handled ? 1 : 0;
+  return conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::plain, 0, true, false).planes != 0 ? 1 : 0;
 }
 
-namespace bcp { int b6_last_planes(); }
 // operand planes of the kernel that serves this shape when the launch carries the tensors' maxima (x_amax ...): 3 = three bf16 planes
 // (six MFMAs per K block), 2 = two fp16 planes (three), 0 = not on the 16-bit matrix pipe at all.  Measurement record (bench.py prices
 // the op against bf16 peak / 6 or / 3 accordingly); no launch.  wgrad != 0: the weight gradient of the same layer.
 extern "C" int bcp_conv3_planes(int N, int D, int H, int W, int Cin, int Cout, int KD, int wgrad) {
   if (Cin % 4 || Cin < 4) return 0;
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  static float dummy;
-  if (wgrad) return b6_wgrad_workspace_bytes(cd, KD) > 0 ? (options().conv3_f16 != 0 ? 2 : 3) : 0;
-  cd.xamax = &dummy;
-  bool handled = false;
-  b6_fwd(nullptr, nullptr, nullptr, nullptr, cd, KD, 0, &dummy, nullptr, 0, true, nullptr, &handled);
-  return handled ? bcp::b6_last_planes() : 0;
+  if (wgrad) {
+    ConvDims cd;
+    fill_dims(cd, N, D, H, W, Cin, Cout);
+    return b6_wgrad_workspace_bytes(cd, KD) > 0 ? (options().conv3_f16 != 0 ? 2 : 3) : 0;
+  }
+  return conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::plain, 0, true, true).planes;
 }
 
 extern "C" int bcp_conv3_last_section(void) { return g_last_section; }
@@ -1638,50 +1680,25 @@ extern "C" size_t bcp_conv3_wgrad_path(int N, int D, int H, int W, int Cin, int 
   return b6_wgrad_workspace_bytes(cd, KD) > 0 ? 1 : 0;       // conv3bw.hip takes the shape
 }
 
-extern "C" int bcp_conv3_fwd_stats(const float* x, const float* wp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
-                                   int Cout, int KD, void* workspace, double* stat_partial, int groups, const float* x_amax_or_null,
-                                   void* stream) {
-  BCP_REQUIRE(x && wp && y && stat_partial, "bcp_conv3_fwd_stats: null pointer");
-  BCP_REQUIRE((KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0 && groups >= 1, "bcp_conv3_fwd_stats: bad extents");
-  BCP_REQUIRE(Cin % 4 == 0 && Cin >= 4, "bcp_conv3_fwd_stats: Cin=%d must be a multiple of 4", Cin);
-  BCP_REQUIRE(aligned16(x) && aligned16(wp), "bcp_conv3_fwd_stats: x / wp must be 16-B aligned");
-  const int rc = conv3_fwd_impl(x, wp, bias, y, N, D, H, W, Cin, Cout, KD, 0, workspace, stat_partial, groups, false, stream, x_amax_or_null);
-  if (rc < 0) return rc;
-  BCP_REQUIRE(rc > 0, "bcp_conv3_fwd_stats: fused statistics unavailable for this shape (check bcp_conv3_stat_rows first)");
-  BCP_CHECK_LAUNCH("bcp_conv3_fwd_stats");
-  return BCP_OK;
-}
-
 // dgrad with the consumer's norm-backward statistics in its epilogue (bf16-pipe kernels only): the conv output is da of the norm
 // layer whose pre-norm tensor is y_prev / statistics stats_prev; stat_partial receives (sum dz, sum dz * xhat) partials
 // [groups][rows][Cout][2], rows = bcp_conv3_bwdstat_rows(...) (0: not available for this shape), to be handed to bcp_norm_bwd as
 // partial_in -- its statistics pass over (y, da) is then skipped.  No dropout epilogues (chan_scale / elem_mask) on that layer.
 extern "C" int bcp_conv3_bwdstat_rows(int N, int D, int H, int W, int Cin, int Cout, int KD, int groups) {
   if (Cin % 4 || Cin < 4 || groups < 1 || options().fuse_bwd_stats == 0) return 0;
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  bool handled = false;
-  static float dummy;
-  const BwdStatsIn bw{&dummy, &dummy, 0};
-  const int rows = b6_fwd(nullptr, nullptr, nullptr, nullptr, cd, KD, 0, &dummy, nullptr, groups, true, nullptr, &handled, nullptr, &bw);
-  return handled && rows > 0 ? rows : 0;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::bwd_stats, groups, true, false);
+  return r.served ? r.rows : 0;
 }
 
 extern "C" int bcp_conv3_dgrad_bwdstats(const float* dy, const float* wp_dgrad, float* da, int N, int D, int H, int W, int Cin, int Cout,
                                         int KD, const float* y_prev, const float* stats_prev, int act, void* workspace,
                                         double* stat_partial, int groups, const float* dy_amax_or_null, void* stream) {
-  BCP_REQUIRE(dy && wp_dgrad && da && y_prev && stats_prev && stat_partial, "bcp_conv3_dgrad_bwdstats: null pointer");
-  BCP_REQUIRE((KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0 && groups >= 1, "bcp_conv3_dgrad_bwdstats: bad extents");
-  BCP_REQUIRE(Cin % 4 == 0 && Cin >= 4, "bcp_conv3_dgrad_bwdstats: Cin=%d must be a multiple of 4", Cin);
-  BCP_REQUIRE(aligned16(dy) && aligned16(wp_dgrad) && aligned16(y_prev), "bcp_conv3_dgrad_bwdstats: dy / wp / y_prev must be 16-B aligned");
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  cd.xamax = dy_amax_or_null;
-  bool handled = false;
+  if (const int rc = conv3_check_args("bcp_conv3_dgrad_bwdstats", dy && wp_dgrad && da && y_prev && stats_prev && stat_partial,
+                                      aligned16(dy) && aligned16(wp_dgrad) && aligned16(y_prev), N, D, H, W, Cin, KD, groups)) return rc;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::bwd_stats, groups, workspace != nullptr, dy_amax_or_null != nullptr);
+  BCP_REQUIRE(r.served && r.rows > 0, "bcp_conv3_dgrad_bwdstats: fused statistics unavailable for this shape (check bcp_conv3_bwdstat_rows first)");
   const BwdStatsIn bw{y_prev, stats_prev, act};
-  const int rows = b6_fwd(dy, wp_dgrad, nullptr, da, cd, KD, 0, workspace, stat_partial, groups, false, (hipStream_t)stream, &handled, nullptr, &bw);
-  BCP_REQUIRE(handled && rows > 0, "bcp_conv3_dgrad_bwdstats: fused statistics unavailable for this shape (check bcp_conv3_bwdstat_rows first)");
-  g_last_section = bcp::b6_last_planes() == 2 ? 4 : 2;
+  if (const int rc = conv3_launch(r, dy, wp_dgrad, nullptr, da, (float*)workspace, stat_partial, &bw, dy_amax_or_null, 0, (hipStream_t)stream)) return rc;
   BCP_CHECK_LAUNCH("bcp_conv3_dgrad_bwdstats");
   return BCP_OK;
 }
@@ -1691,39 +1708,21 @@ extern "C" int bcp_conv3_dgrad_bwdstats(const float* dy, const float* wp_dgrad, 
 // how many slabs the launch will write for this shape under the current options (1..8), or 0: shape not served in raw mode (use
 // bcp_conv3_fwd).  Forward and dgrad alike (dgrad = the flipped pack).
 extern "C" int bcp_conv3_fwd_nslabs(int N, int D, int H, int W, int Cin, int Cout, int KD) {
-  if (Cin % 4 || Cin < 4 || (KD != 1 && KD != 3) || N < 1 || D < 1 || H < 1 || W < 1) return 0;
-  if ((long long)N * D * H * W * Cout > options().conv3_sk_elems) return 0;      // the slab buffer is sized like bcp_conv3_fwd_workspace_bytes: deep levels only
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  bool handled = false;
-  static float dummy;
-  int sk = 0;
-  b6_fwd(nullptr, nullptr, nullptr, &dummy, cd, KD, 0, &dummy, nullptr, 0, true, nullptr, &handled, &sk);
-  return handled ? sk : 0;
+  if (!conv3_shape_ok(N, D, H, W, Cin, KD)) return 0;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::raw, 0, true, false);
+  return r.served ? r.sk : 0;
 }
 
 extern "C" int bcp_conv3_fwd_raw(const float* x, const float* wp, float* slabs, int nslab, int N, int D, int H, int W, int Cin, int Cout,
                                  int KD, const float* x_amax_or_null, void* stream) {
-  BCP_REQUIRE(x && wp && slabs, "bcp_conv3_fwd_raw: null pointer");
-  BCP_REQUIRE((KD == 1 || KD == 3) && N > 0 && D > 0 && H > 0 && W > 0, "bcp_conv3_fwd_raw: bad extents");
-  BCP_REQUIRE(KD == 3 || D == 1, "bcp_conv3_fwd_raw: KD=1 needs D=1");
-  BCP_REQUIRE(Cin % 4 == 0 && Cin >= 4, "bcp_conv3_fwd_raw: Cin=%d must be a multiple of 4", Cin);
-  BCP_REQUIRE(aligned16(x) && aligned16(wp) && aligned16(slabs), "bcp_conv3_fwd_raw: x / wp / slabs must be 16-B aligned");
+  if (const int rc = conv3_check_args("bcp_conv3_fwd_raw", x && wp && slabs, aligned16(x) && aligned16(wp) && aligned16(slabs), N, D, H, W, Cin, KD, 1)) return rc;
   BCP_REQUIRE((long long)N * D * H * W * Cout <= options().conv3_sk_elems, "bcp_conv3_fwd_raw: output too large for raw slabs (check bcp_conv3_fwd_nslabs)");
-  ConvDims cd;
-  fill_dims(cd, N, D, H, W, Cin, Cout);
-  bool handled = false;
-  int sk = 0;
-  // the caller sized `slabs` for nslab slabs: the count the launch will write under the CURRENT options must be that one (a count
-  // cached under other options would be a device buffer overflow) -- dry run first, nothing is launched on a mismatch
-  b6_fwd(nullptr, nullptr, nullptr, slabs, cd, KD, 0, slabs, nullptr, 0, true, nullptr, &handled, &sk);
-  BCP_REQUIRE(handled && sk > 0, "bcp_conv3_fwd_raw: shape not served in raw mode (check bcp_conv3_fwd_nslabs first)");
-  BCP_REQUIRE(sk == nslab, "bcp_conv3_fwd_raw: the launch writes %d slabs under the current options, the caller allocated %d (stale bcp_conv3_fwd_nslabs answer?)", sk, nslab);
-  handled = false;
-  cd.xamax = x_amax_or_null;
-  b6_fwd(x, wp, nullptr, slabs, cd, KD, 0, slabs, nullptr, 0, false, (hipStream_t)stream, &handled, &sk);
-  BCP_REQUIRE(handled && sk == nslab, "bcp_conv3_fwd_raw: shape not served in raw mode (check bcp_conv3_fwd_nslabs first)");
-  g_last_section = bcp::b6_last_planes() == 2 ? 4 : 2;
+  const Conv3Route r = conv3_route(N, D, H, W, Cin, Cout, KD, Conv3Mode::raw, 0, true, x_amax_or_null != nullptr);
+  BCP_REQUIRE(r.served, "bcp_conv3_fwd_raw: shape not served in raw mode (check bcp_conv3_fwd_nslabs first)");
+  // the caller sized `slabs` for nslab slabs: the count the launch writes under the CURRENT options must be that one (a count cached
+  // under other options would be a device buffer overflow) -- nothing is launched on a mismatch
+  BCP_REQUIRE(r.sk == nslab, "bcp_conv3_fwd_raw: the launch writes %d slabs under the current options, the caller allocated %d (stale bcp_conv3_fwd_nslabs answer?)", r.sk, nslab);
+  if (const int rc = conv3_launch(r, x, wp, nullptr, slabs, nullptr, nullptr, nullptr, x_amax_or_null, 0, (hipStream_t)stream)) return rc;
   BCP_CHECK_LAUNCH("bcp_conv3_fwd_raw");
   return BCP_OK;
 }
@@ -1841,22 +1840,35 @@ static void c1_launch(int KD, dim3 grid, hipStream_t s, const float* x, const fl
   else hipLaunchKernelGGL((k_conv3_c1<1, 1, 16, 16, EPI>), grid, dim3(256), 0, s, x, w, bias, y, cd, tiles, tpb, st, nm);
 }
 
-// epi: the kernel's EPI mode; returns the statistics rows per group (0: groups do not divide the batch)
-static int c1_fwd_impl(const float* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int KD, double* stat_partial,
-                       int groups, bool dry, hipStream_t s, int epi = 0, const C1Norm* nmp = nullptr) {
+static void c1_tile_counts(ConvDims& cd, int KD) {
+  if (KD == 3) { cd.tiles_d = cdiv(cd.D, 4); cd.tiles_h = cdiv(cd.H, 4); cd.tiles_w = cdiv(cd.W, 16); }
+  else { cd.tiles_d = 1; cd.tiles_h = cdiv(cd.H, 16); cd.tiles_w = cdiv(cd.W, 16); }
+}
+
+// statistics rows per group the first-layer launch writes (0: groups do not divide the batch); the query's answer and the launch's row count
+static int c1_stat_rows(int N, int D, int H, int W, int KD, int groups) {
+  if (groups < 1 || N % groups) return 0;                 // tiles are sample-major: a group = whole samples
   ConvDims cd;
   fill_dims(cd, N, D, H, W, 1, 16);
-  if (KD == 3) { cd.tiles_d = cdiv(D, 4); cd.tiles_h = cdiv(H, 4); cd.tiles_w = cdiv(W, 16); }
-  else { cd.tiles_d = 1; cd.tiles_h = cdiv(H, 16); cd.tiles_w = cdiv(W, 16); }
+  c1_tile_counts(cd, KD);
+  const int tpg = N * cd.tiles_d * cd.tiles_h * cd.tiles_w / groups;
+  return tpg / c1_tiles_per_block(tpg);
+}
+
+// epi: the kernel's EPI mode; returns the statistics rows per group (0 with groups > 0: groups do not divide the batch, nothing is launched)
+static int c1_fwd_impl(const float* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int KD, double* stat_partial,
+                       int groups, hipStream_t s, int epi = 0, const C1Norm* nmp = nullptr) {
+  ConvDims cd;
+  fill_dims(cd, N, D, H, W, 1, 16);
+  c1_tile_counts(cd, KD);
   const int tiles = N * cd.tiles_d * cd.tiles_h * cd.tiles_w;
   StatsArg st{nullptr, 0, 1, 16, groups > 0 ? groups : 1};
   int tpb = 1;
   if (groups > 0) {
-    if (N % groups) return 0;                             // tiles are sample-major: a group = whole samples
-    const int tpg = tiles / groups;
-    tpb = c1_tiles_per_block(tpg);
-    st.tiles_per_group = tpg; st.rows = tpg / tpb; st.partial = stat_partial;
-    if (dry) return st.rows;
+    st.rows = c1_stat_rows(N, D, H, W, KD, groups);
+    if (st.rows == 0) return 0;
+    st.tiles_per_group = tiles / groups; st.partial = stat_partial;
+    tpb = st.tiles_per_group / st.rows;
   }
   const dim3 grid(cdiv(tiles, tpb));
   const C1Norm none{nullptr, nullptr, nullptr, nullptr, 1.f, 0, 1, nullptr};
@@ -1877,7 +1889,7 @@ extern "C" int bcp_conv3_c1_fwd(const float* x, const float* w, const float* bia
   BCP_REQUIRE(x && w && y, "bcp_conv3_c1_fwd: null pointer");
   BCP_REQUIRE((KD == 1 && D == 1) || KD == 3, "bcp_conv3_c1_fwd: bad KD/D");
   BCP_REQUIRE(aligned16(y) && (!bias || aligned16(bias)), "bcp_conv3_c1_fwd: y / bias must be 16-B aligned");
-  c1_fwd_impl(x, w, bias, y, N, D, H, W, KD, nullptr, 0, false, (hipStream_t)stream);
+  c1_fwd_impl(x, w, bias, y, N, D, H, W, KD, nullptr, 0, (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_conv3_c1_fwd");
   return BCP_OK;
 }
@@ -1887,7 +1899,7 @@ extern "C" int bcp_conv3_c1_fwd(const float* x, const float* w, const float* bia
 // needs no statistics pass over its 64-byte-per-voxel output
 extern "C" int bcp_conv3_c1_stat_rows(int N, int D, int H, int W, int KD, int groups) {
   if (groups < 1 || N < 1 || D < 1 || H < 1 || W < 1 || !((KD == 1 && D == 1) || KD == 3)) return 0;
-  return c1_fwd_impl(nullptr, nullptr, nullptr, nullptr, N, D, H, W, KD, nullptr, groups, true, nullptr);
+  return c1_stat_rows(N, D, H, W, KD, groups);
 }
 
 extern "C" int bcp_conv3_c1_fwd_stats(const float* x, const float* w, const float* bias, float* y, int N, int D, int H, int W, int KD,
@@ -1895,7 +1907,7 @@ extern "C" int bcp_conv3_c1_fwd_stats(const float* x, const float* w, const floa
   BCP_REQUIRE(x && w && y && stat_partial && groups >= 1, "bcp_conv3_c1_fwd_stats: null pointer / bad groups");
   BCP_REQUIRE((KD == 1 && D == 1) || KD == 3, "bcp_conv3_c1_fwd_stats: bad KD/D");
   BCP_REQUIRE(aligned16(y) && (!bias || aligned16(bias)), "bcp_conv3_c1_fwd_stats: y / bias must be 16-B aligned");
-  const int rows = c1_fwd_impl(x, w, bias, y, N, D, H, W, KD, stat_partial, groups, false, (hipStream_t)stream);
+  const int rows = c1_fwd_impl(x, w, bias, y, N, D, H, W, KD, stat_partial, groups, (hipStream_t)stream);
   BCP_REQUIRE(rows > 0, "bcp_conv3_c1_fwd_stats: fused statistics unavailable (N %% groups != 0): check bcp_conv3_c1_stat_rows first");
   BCP_CHECK_LAUNCH("bcp_conv3_c1_fwd_stats");
   return BCP_OK;
@@ -1927,12 +1939,12 @@ extern "C" int bcp_conv3_c1_norm_fwd(const float* x, const float* w, const float
   BCP_REQUIRE(aligned16(out) && aligned16(stats) && (!bias || aligned16(bias)), "bcp_conv3_c1_norm_fwd: alignment");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(workspace);
-  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, false, s, 1);
+  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, s, 1);
   BCP_REQUIRE(rows > 0, "bcp_conv3_c1_norm_fwd: the groups must be whole samples (N %% groups == 0)");
   norm_fwd_finalize_launch(partial, rows, groups, 16, (long long)N / groups * D * H * W, gamma, beta, running_mean, running_var, momentum, eps, stats, s,
                            amax_out_or_null);
   const C1Norm nm{stats, nullptr, nullptr, elem_mask, elem_scale, act, groups, amax_out_or_null, mask_seed, mask_p_keep};
-  c1_fwd_impl(x, w, bias, out, N, D, H, W, KD, nullptr, groups, false, s, 2, &nm);
+  c1_fwd_impl(x, w, bias, out, N, D, H, W, KD, nullptr, groups, s, 2, &nm);
   BCP_CHECK_LAUNCH("bcp_conv3_c1_norm_fwd");
   return BCP_OK;
 }
@@ -1951,9 +1963,9 @@ extern "C" int bcp_conv3_c1_norm_bwd(const float* x, const float* w, const float
   BCP_REQUIRE(rows0 > 0, "bcp_conv3_c1_norm_bwd: the groups must be whole samples (N %% groups == 0)");
   float* c1c2raw = reinterpret_cast<float*>(partial + (size_t)groups * rows0 * 16 * 2);
   C1Norm nm{stats, da, c1c2raw, elem_mask, elem_scale, act, groups, nullptr, mask_seed, mask_p_keep};
-  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, false, s, 3, &nm);
+  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, s, 3, &nm);
   norm_bwd_finalize_launch(partial, rows, groups, 16, (long long)N / groups * D * H * W, dgamma, dbeta, accumulate, c1c2raw, s, nullptr);
-  c1_fwd_impl(x, w, bias, dy, N, D, H, W, KD, nullptr, groups, false, s, 4, &nm);
+  c1_fwd_impl(x, w, bias, dy, N, D, H, W, KD, nullptr, groups, s, 4, &nm);
   BCP_CHECK_LAUNCH("bcp_conv3_c1_norm_bwd");
   return BCP_OK;
 }
@@ -1983,9 +1995,9 @@ extern "C" int bcp_conv3_c1_norm_bwd_wgrad(const float* x, const float* w, const
   float* c1c2raw = reinterpret_cast<float*>(partial + (size_t)groups * rows0 * 16 * 2);
   float* wpart = c1c2raw + (size_t)4 * groups * 16;            // [groups * rows0 workgroups][T][16]
   C1Norm nm{stats, da, c1c2raw, elem_mask, elem_scale, act, groups, nullptr, mask_seed, mask_p_keep};
-  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, false, s, 3, &nm);
+  const int rows = c1_fwd_impl(x, w, bias, nullptr, N, D, H, W, KD, partial, groups, s, 3, &nm);
   norm_bwd_finalize_launch(partial, rows, groups, 16, (long long)N / groups * D * H * W, dgamma, dbeta, accumulate, c1c2raw, s, nullptr);
-  c1_fwd_impl(x, w, bias, wpart, N, D, H, W, KD, nullptr, groups, false, s, 5, &nm);
+  c1_fwd_impl(x, w, bias, wpart, N, D, H, W, KD, nullptr, groups, s, 5, &nm);
   const int G = groups * rows, T = KD * 9;                     // workgroups of pass 2 = statistics rows of pass 1 (same tiling)
   if (G >= 32 || options().wgrad_reduce_flat == 2)      // (2: tests force the flat sum for every group count)
     launch_reduce_deep(wpart, dw, G, T, 1, 16, 1, 16, dw_accumulate, s);

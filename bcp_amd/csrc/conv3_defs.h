@@ -371,4 +371,69 @@ __host__ __device__ __forceinline__ long long pack_off_hdr(int T, int K16, int N
 
 struct Cfg { int KD, TD, TH, TW, NT, WT; };
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// The forward / dgrad dispatch of the 3x3(x3) conv as a record: conv3_route() DECIDES (a pure function of the shape, the mode and
+// options(): no pointer, no HIP call, no global), conv3_launch() only executes what the record says, and the shape queries
+// (bcp_conv3_stat_rows, _fwd_nslabs, _bwdstat_rows, _fwd_path, _planes) return its fields.  A query and a launch cannot disagree.
+enum class Conv3Family { none, mfma, res, c3b, c3h, c3p, c3d, c3f, c3q };      // k_conv3_mfma / k_conv3_res (conv3.hip), the rest conv3b.hip
+enum class Conv3Mode {
+  plain,      // bcp_conv3_fwd
+  fwd_stats,  // bcp_conv3_fwd_stats: (sum y, sum y^2) partial rows in the epilogue
+  raw,        // bcp_conv3_fwd_raw: the sk split-K slabs are the result (bf16-pipe kernels only)
+  bwd_stats   // bcp_conv3_dgrad_bwdstats: the consumer norm layer's backward statistics in the epilogue (bf16-pipe kernels only)
+};
+struct Conv3Route {
+  ConvDims cd{};            // the shape, with the instance's tile counts; xamax / yamax stay null (the launch supplies its pointer)
+  int groups = 1;           // normalisation groups of the statistics rows
+  bool served = false;      // false: not in this mode (statistics rows 0, no raw slabs, no backward-statistics instance): nothing else is valid
+  Conv3Family family = Conv3Family::none;
+  int KD = 0, TD = 0, TH = 0, TW = 0, NT = 0;      // the instance's tile and channel slab (NT x 16); flat kernels (c3f / c3q): no tile
+  int SP = 0;               // k_c3b / k_c3f: tap pairs per weight stage; k_conv3_mfma: WT, taps per weight stage
+  int planes = 0;           // operand planes: 0 = fp32 operands, 3 = three bf16 pieces, 2 = two fp16 pieces (the launch carries |max|)
+  bool persistent = false;  // k_c3d: workgroups walk several tiles (PER)
+  bool wlds = false;        // k_c3d: the one cin chunk's weight fragments in the LDS (WL, option c3d16_form)
+  bool bw = false;          // the backward-statistics epilogue (BW)
+  int sk = 1;               // split-K factor = gridDim.z; > 1 writes slabs
+  bool sum_slabs = false;   // ... which a slab-sum launch folds into y (not in raw mode)
+  unsigned gx = 0, gy = 0;  // gridDim.x / .y
+  size_t lds = 0;           // dynamic LDS of the launch
+  int tiles = 0;            // the kernel's tile-count argument (k_conv3_res, k_c3d: spatial tiles; k_c3f / k_c3q: tiles per sample)
+  int rows = 0;             // statistics rows per group the launch writes (fwd_stats / bwd_stats)
+  int tiles_per_group = 0;  // spatial tiles per normalisation group
+  int section = 0;          // which section of the packed weight the launch reads: 1 fp32, 2 three bf16 planes, 4 two fp16 planes
+};
+Conv3Route conv3_route(const ConvDims& cd, int KD, Conv3Mode mode, int groups, bool has_workspace, bool has_amax);
+
+// Split-K over the cin chunks, where a workspace for the slabs exists.  Brick tiles (deep levels: too few tiles to fill 256 CUs): up to 4
+// slabs once the grid is no larger than the CU count.  Flat tiles: a deep-level workgroup's life is a serial chain of weight stages (one
+// barrier per tap pair), so the chain is cut as short as the grid allows -- the largest power of two (<= 8, >= 2 chunks per workgroup) that
+// keeps the launch within the 512 co-resident workgroup slots; measured alone (fwd + statistics, us): 256 channels batch 2 / 4: 31.3 -> 25.8 /
+// 40.7 -> 34.3 (with 64-channel slabs at batch 4); 128 channels batch 4: 67.2 -> 59.4 (split 2: 496 workgroups instead of 992)
+inline int conv3_split_k(long long blocks, int nch, bool flat) {
+  const Options& o = options();
+  int sk = 1;
+  if (nch >= 4 && !flat && blocks <= 256) sk = nch / 2 < 4 ? nch / 2 : 4;
+  if (nch >= 4 && flat) {
+    const int cap = nch / 2 < 8 ? nch / 2 : 8;
+    while (sk * 2 <= cap && blocks * sk * 2 <= 512) sk *= 2;
+  }
+  if (o.splitk >= 1 && o.splitk <= 4 && o.splitk <= nch) sk = o.splitk;
+  if (flat && o.conv3_b6_flat_sk >= 1 && o.conv3_b6_flat_sk <= 8 && o.conv3_b6_flat_sk <= nch) sk = o.conv3_b6_flat_sk;      // measurement override
+  return sk;
+}
+
+// what conv3_launch() launches for a record: kernels of three argument lists (a: k_conv3_mfma, k_c3b, k_c3h, k_c3p; t, with a tile count:
+// k_c3d, k_c3f, k_c3q; res: k_conv3_res), and the family's slab-sum kernel
+typedef void (*Conv3KernelA)(const float*, const float*, const float*, float*, ConvDims, int, StatsArg);
+typedef void (*Conv3KernelT)(const float*, const float*, const float*, float*, ConvDims, int, int, StatsArg);
+typedef void (*Conv3KernelRes)(const float*, const float*, const float*, float*, ConvDims, int, int, StatsArg, int);
+typedef void (*Conv3KernelSum)(const float*, int, long long, int, const float*, float*, int);
+struct Conv3Kernel {
+  Conv3KernelA a = nullptr;
+  Conv3KernelT t = nullptr;
+  Conv3KernelRes res = nullptr;
+  Conv3KernelSum sum = nullptr;
+  const void* fn() const { return a ? reinterpret_cast<const void*>(a) : t ? reinterpret_cast<const void*>(t) : reinterpret_cast<const void*>(res); }
+};
+
 }  // namespace bcp

@@ -17,7 +17,7 @@
 // [piece][pair][cout][32 k] copied from the pre-split bf16 pack the weight packer writes behind the fp32 pack.  Two workgroups per
 // CU: one computes while the other refills (the halo split is ~22 VALU per float4: v_cvt_pk_bf16_f32).
 //
-// Kernel families in this file (which one serves a shape: b6_fwd at the end; DESIGN.md sections 3a / 3b):
+// Kernel families in this file (which one serves a shape: b6_route at the end; DESIGN.md sections 3a / 3b):
 //   k_c3d  weight fragments straight from global memory, no barrier in the tap loop, fragment stream; 32-channel slabs on 256-voxel
 //          tiles, and -- persistent, next tile's halo under the current tile's MFMAs -- the 16 -> 16 layers (3-D and 2-D)
 //   k_c3p  64-voxel x 64-channel tiles as an LDS-DMA software pipeline (round 3): weight ring of three slots filled by
@@ -1713,10 +1713,14 @@ __global__ __launch_bounds__(256) void k_b6_sum_slabs(const float* __restrict__ 
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------
+// host side: the bf16-pipe half of conv3_route() (b6_route: which tile, which kernel family, which grid) and of conv3_launch()
+// (b6_kernel: the record -> the kernel instance).  Both are called from conv3.hip.
+// ------------------------------------------------------------------------------------------------------------------------------
+
 // tile configurations whose dgrad launches carry the backward-statistics epilogue (bcp_conv3_dgrad_bwdstats): the conv -> conv edges of
 // the V-Nets' 32- / 64-channel levels and of the U-Net's decoder blocks; everything else answers "not available" and takes the plain dgrad
-template <int KD, int TD, int TH, int TW, int NT, int SP>
-constexpr bool b6_has_bw() {
+constexpr bool b6_has_bw(int KD, int TD, int TH, int TW, int NT, int SP) {
   return (KD == 3 && TD == 4 && TH == 8 && TW == 8 && NT == 2 && SP == 1) || (KD == 3 && TD == 4 && TH == 4 && TW == 8 && NT == 2 && SP == 1) ||
          (KD == 3 && TD == 4 && TH == 4 && TW == 4 && NT == 4 && SP == 1) || (KD == 1 && TD == 1 && TH == 16 && TW == 16 && NT == 2 && SP == 1) ||
          (KD == 1 && TD == 1 && TH == 8 && TW == 16 && NT == 2 && SP == 2);
@@ -1725,8 +1729,7 @@ constexpr bool b6_has_bw() {
 
 // tile configurations that have a two-plane fp16 instance (PL = 2; selected when the launch carries the input's |max| and option conv3_f16
 // allows it): round 4 -- the direct-weight kernel k_c3d (16- / 32-channel slabs, 3-D and 2-D)
-template <int KD, int TD, int TH, int TW, int NT, int SP>
-constexpr bool b6_has_f16() {
+constexpr bool b6_has_f16(int KD, int TD, int TH, int TW, int NT, int SP) {
   return SP == 1 && ((KD == 3 && TD == 4 && TH == 8 && TW == 8 && (NT == 1 || NT == 2)) || (KD == 3 && TD == 4 && TH == 4 && TW == 8 && NT == 2) ||
                      (KD == 1 && TD == 1 && TH == 16 && TW == 16 && (NT == 1 || NT == 2)) ||
                      (KD == 1 && TD == 1 && TH == 8 && TW == 16 && NT == 4) ||      // k_c3b, the U-Net's 64-channel-slab kernel
@@ -1735,300 +1738,137 @@ constexpr bool b6_has_f16() {
 
 // tile configurations whose 32-channel-slab two-plane instance of k_c3d also exists in the persistent one-row-per-tile form (option
 // c3d32_form): the 3-D 4x8x8 tile.  (The 2-D 16x16 instances stay one tile per workgroup.)
-template <int KD, int TD, int TH, int TW, int NT, int SP>
-constexpr bool b6_has_per32() { return SP == 1 && KD == 3 && TD == 4 && TH == 8 && TW == 8 && NT == 2; }
+constexpr bool b6_has_per32(int KD, int TD, int TH, int TW, int NT, int SP) { return SP == 1 && KD == 3 && TD == 4 && TH == 8 && TW == 8 && NT == 2; }
 // ... and whether its backward-statistics instance takes that form too (it passes the same register gate once the launch-invariant lane values
 // are rebuilt per item: DESIGN.md section 3a)
 static constexpr bool b6_per32_bw = true;
 
-// dynamic LDS of k_c3p: two halo buffers, three weight slots, statistics scratch
-template <class TL, int PL = 3>
-static constexpr size_t kC3pLds = (size_t)2 * PL * TL::HV * XSB * 2 + (size_t)3 * PL * 64 * 32 * 2 + (size_t)4 * 32 * 2 * sizeof(double);
-
-// measurement record (bcp_conv3_fwd_planes): how many operand planes the last launcher call on this thread chose (dry runs included)
-thread_local int g_b6_last_planes = 3;
-
-template <int KD, int TD, int TH, int TW, int NT, int SP>
-static int b6_launch(const float* X, const float* Wp, const float* bias, float* Y, ConvDims cd, int accumulate, float* ws,
-                     double* stat_partial, int G, bool dry, hipStream_t s, int* raw_sk, const BwdStatsIn* bw) {
-  using TL = Tile<KD, TD, TH, TW>;
-  constexpr int CT = NT * 16;
-  // k_c3d only where a wave's weight traffic is small next to its MFMAs: 256-voxel tiles with a 32-channel slab (6 KB per 48 MFMAs;
-  // the 64-voxel / 64-channel instances would pull 12 KB per 24 MFMAs through L1: 79-84 vs 47-51 us)
-  const bool direct = options().conv3_b6_direct != 0 && (options().conv3_b6_direct >= 2 || (TL::MT == 4 && NT <= 2));
-  // two fp16 planes instead of three bf16 ones: the launch must carry the input's |max| (cd.xamax) and the instance must exist
-  const bool pipe64 = TL::M == 64 && NT == 4 && SP == 1 && options().conv3_b6_w22 != 0 && options().conv3_b6_pipe != 0;      // -> k_c3p
-  const bool staged2d = KD == 1 && NT == 4;                                                       // -> k_c3b itself
-  const bool use_f16 = b6_has_f16<KD, TD, TH, TW, NT, SP>() && (staged2d || (NT == 4 ? pipe64 : direct)) && cd.xamax != nullptr && options().conv3_f16 != 0;
-  if (!use_f16) cd.xamax = nullptr;
-  const int npl = use_f16 ? 2 : 3;
-  g_b6_last_planes = npl;
-  const size_t lds = (size_t)npl * TL::HV * XSB * 2 + (direct ? 0 : (size_t)2 * npl * SP * CT * 32 * 2) + (size_t)4 * CT * 2 * sizeof(double);
-  cd.tiles_d = cdiv(cd.D, TD); cd.tiles_h = cdiv(cd.H, TH); cd.tiles_w = cdiv(cd.W, TW);
-  auto kfn = k_c3b<KD, TD, TH, TW, NT, SP>;
-  if constexpr (KD == 1 && NT == 4 && b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
-    if (use_f16) kfn = k_c3b<KD, TD, TH, TW, NT, SP, false, 2>;       // the U-Net's 64-channel slabs on two fp16 planes
-  }
-  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int gx = cd.N * cd.tiles_d * cd.tiles_h * cd.tiles_w, gy = cd.Cout16 / CT;
-  const int nch = cd.Cin16 / 16;
-  int sk = 1;
-  const bool ws_fits = ws && (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout <= options().conv3_sk_elems;     // bcp_conv3_fwd_workspace_bytes
-  if (ws_fits && (long long)gx * gy <= 256 && nch >= 4) { sk = nch / 2; if (sk > 4) sk = 4; }
-  { const int f = options().splitk; if (ws_fits && f >= 1 && f <= 4 && f <= nch) sk = f; }
-  if (raw_sk) {
-    // raw mode (bcp_conv3_fwd_raw): the sk partial slabs go to Y = float[sk][N*D*H*W*Cout] and stay there -- no bias, no slab sum, no
-    // statistics; the consumer (bcp_norm_fwd_slabs / bcp_norm_bwd_slabs) sums them on its way in
-    *raw_sk = sk;
-    if (dry) return 0;
-    StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-    if (direct && NT != 1) {                           // (16-channel slabs: the persistent form of k_c3d is not a slab writer; staged kernel)
-      auto kd = k_c3d<KD, TD, TH, TW, NT, false>;
-      if constexpr (b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
-        if (use_f16) kd = k_c3d<KD, TD, TH, TW, NT, false, false, 2>;
-      }
-      hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kd, dim3(gx, gy, sk), dim3(256), lds, s, X, Wp, (const float*)nullptr, Y, cd, gx, 0, none);
-    } else {
-      // the STAGED kernel always needs its weight stage: `lds` left it out when `direct` chose k_c3d (16-channel slabs
-      // come here with direct && NT == 1 and overran their allocation by the 6 KB stage)
-      size_t lds_k = lds + (direct ? (size_t)2 * npl * SP * CT * 32 * 2 : 0);
-      if constexpr (TL::M == 64 && NT == 4 && SP == 1) {
-        if (options().conv3_b6_w22 != 0) kfn = k_c3h<KD, TD, TH, TW>;
-        if (options().conv3_b6_w22 != 0 && options().conv3_b6_pipe != 0) {
-          kfn = k_c3p<KD, TD, TH, TW>; lds_k = kC3pLds<TL>;
-          if constexpr (b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
-            if (use_f16) { kfn = k_c3p<KD, TD, TH, TW, false, 2>; lds_k = kC3pLds<TL, 2>; }
-          }
-        }
-      }
-      if (lds_k > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);
-      hipLaunchKernelGGL(kfn, dim3(gx, gy, sk), dim3(256), lds_k, s, X, Wp, (const float*)nullptr, Y, cd, 0, none);
-    }
-    return 0;
-  }
-  StatsArg st{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
-  if (sk == 1 && G > 0 && gx % G == 0) { st.rows = gx / G; st.tiles_per_group = gx / G; st.partial = stat_partial; }
-  if (bw) {                                           // backward statistics in the epilogue (bcp_conv3_dgrad_bwdstats): one-pass launches only
-    if (!b6_has_bw<KD, TD, TH, TW, NT, SP>() || sk != 1 || G <= 0 || gx % G || (direct && NT == 1)) return 0;
-    if (options().fuse_bwd_stats == 2 && KD == 3 && NT == 2) return 0;      // measurement: not at the 3-D 32-channel slabs (k_c3d's epilogue: +39 us per launch)
-    st.by = bw->y; st.bstats = bw->stats; st.bact = bw->act;
-  }
-  if (direct) {
-    // persistent grid (16-channel slabs): tiles dealt round-robin to P workgroups (two per CU), balanced: every workgroup gets
-    // cdiv(tiles, slots) tiles; 32-channel slabs: one tile per workgroup (register budget, see k_c3d) except PT below
-    constexpr bool PER = NT == 1;
-    // PT (option c3d32_form): the 3-D 32-channel slabs on two fp16 planes as persistent workgroups too -- the same balanced deal and XCD walk,
-    // but still ONE STATISTICS ROW PER TILE, so the row count below (and with it every planner's answer) does not depend on the form
-    bool PT = false;
-    if constexpr (b6_has_per32<KD, TD, TH, TW, NT, SP>()) PT = use_f16 && sk == 1 && options().c3d32_form != 0 && (!bw || b6_per32_bw);
-    const int slots = 512 / (gy * sk) > 0 ? 512 / (gy * sk) : 1;
-    const int per = (PER || PT) ? cdiv(gx, slots) : 1;
-    int P = cdiv(gx, per);
-    if ((PER || PT) && (cd.xcd & 2) && P >= 8) P = (P + 7) & ~7;                                           // the XCD-aware walk needs whole rounds of the 8 XCDs
-    if ((PER || PT) && options().conv3_p > 0 && options().conv3_p < P) P = options().conv3_p;      // tests: few workgroups, many tiles each
-    StatsArg sd{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
-    if (sk == 1 && G > 0 && gx % G == 0) { sd.rows = PER ? P : gx / G; sd.tiles_per_group = gx / G; sd.partial = stat_partial; }
-    if (bw) { sd.by = bw->y; sd.bstats = bw->stats; sd.bact = bw->act; }
-    if (dry) return (sk == 1 && G > 0 && gx % G == 0) ? (PER ? P : gx / G) : 0;
-    auto kd = k_c3d<KD, TD, TH, TW, NT, PER>;
-    if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>() && !PER) {
-      if (bw) kd = k_c3d<KD, TD, TH, TW, NT, PER, true>;
-    }
-    size_t lds_d = lds;
-    if constexpr (b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
-      if (use_f16) {
-        kd = k_c3d<KD, TD, TH, TW, NT, PER, false, 2>;
-        if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>() && !PER) {
-          if (bw) kd = k_c3d<KD, TD, TH, TW, NT, PER, true, 2>;
-        }
-        if constexpr (b6_has_per32<KD, TD, TH, TW, NT, SP>()) {
-          if (PT) {
-            kd = k_c3d<KD, TD, TH, TW, NT, true, false, 2>;
-            if constexpr (b6_per32_bw && b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
-              if (bw) kd = k_c3d<KD, TD, TH, TW, NT, true, true, 2>;
-            }
-          }
-        }
-        if constexpr (PER) {
-          // the weight fragments of the one cin chunk in the LDS (option c3d16_form): 14 pairs x 2 planes x 1 KB at the 3-D tile,
-          // 68 KB per workgroup with the halo planes -- still two workgroups per CU
-          if (options().c3d16_form != 0 && cd.Cin16 == 16 && sk == 1) {
-            kd = k_c3d<KD, TD, TH, TW, NT, PER, false, 2, true>;
-            lds_d += (size_t)((TL::T + 1) / 2) * 2 * 64 * 16;
-          }
-        }
-      }
-    }
-    hipFuncSetAttribute(reinterpret_cast<const void*>(kd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_d);
-    if (sk == 1) {
-      hipLaunchKernelGGL(kd, dim3(P, gy, 1), dim3(256), lds_d, s, X, Wp, bias, Y, cd, gx, accumulate, sd);
-    } else {
-      const long long n = (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout;
-      StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-      hipLaunchKernelGGL(kd, dim3(P, gy, sk), dim3(256), lds_d, s, X, Wp, (const float*)nullptr, ws, cd, gx, 0, none);
-      hipLaunchKernelGGL(k_b6_sum_slabs, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, sk, n, cd.Cout, bias, Y,
-                         accumulate);
-    }
-    return sd.partial ? sd.rows : 0;
-  }
-  if (dry) return sk == 1 && G > 0 && gx % G == 0 ? gx / G : 0;
-  if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
-    if (bw) {
-      kfn = k_c3b<KD, TD, TH, TW, NT, SP, true>;
-      if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-  }
-  size_t lds_k = lds;
-  if constexpr (TL::M == 64 && NT == 4 && SP == 1) {
-    if (options().conv3_b6_w22 != 0) {
-      kfn = k_c3h<KD, TD, TH, TW>;       // 2 x 2 wave arrangement of the 64 x 64 tile (same LDS layout and size)
-      if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
-        if (bw) kfn = k_c3h<KD, TD, TH, TW, true>;
-      }
-      if (options().conv3_b6_pipe != 0) {   // the same tile as an LDS-DMA software pipeline (its own LDS layout)
-        kfn = k_c3p<KD, TD, TH, TW>;
-        if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
-          if (bw) kfn = k_c3p<KD, TD, TH, TW, true>;
-        }
-        lds_k = kC3pLds<TL>;
-        if constexpr (b6_has_f16<KD, TD, TH, TW, NT, SP>()) {
-          if (use_f16) {
-            kfn = k_c3p<KD, TD, TH, TW, false, 2>;
-            if constexpr (b6_has_bw<KD, TD, TH, TW, NT, SP>()) {
-              if (bw) kfn = k_c3p<KD, TD, TH, TW, true, 2>;
-            }
-            lds_k = kC3pLds<TL, 2>;
-          }
-        }
-      }
-      if (lds_k > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_k);
-    }
-  }
-  if (sk == 1) {
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, 1), dim3(256), lds_k, s, X, Wp, bias, Y, cd, accumulate, st);
-  } else {
-    const long long n = (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout;
-    StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, sk), dim3(256), lds_k, s, X, Wp, (const float*)nullptr, ws, cd, 0, none);
-    hipLaunchKernelGGL(k_b6_sum_slabs, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, sk, n, cd.Cout, bias, Y,
-                       accumulate);
-  }
-  return st.partial ? st.rows : 0;
-}
+// the 64-voxel x 64-channel tiles: k_c3b's 1 x 4 wave arrangement has the twins k_c3h (2 x 2) and k_c3p (LDS-DMA software pipeline)
+constexpr bool b6_is_64x64(int TD, int TH, int TW, int NT, int SP) { return TD * TH * TW == 64 && NT == 4 && SP == 1; }
 
 static constexpr int kB6FlatAvMax = 384;    // flat halo rows (BM + 2 R) the flat instances hold: 3 x 384 x 32 B = 36 KB
 
-template <int KD, int NT, int SP>
-static int b6_launch_flat(const float* X, const float* Wp, const float* bias, float* Y, ConvDims cd, int accumulate, float* ws,
-                          double* stat_partial, int G, bool dry, hipStream_t s, int* raw_sk, const BwdStatsIn* bw) {
-  constexpr int CT = NT * 16, BM = 64;
-  const int V = cd.D * cd.H * cd.W, tps = cdiv(V, BM);
-  size_t lds = (size_t)3 * kB6FlatAvMax * XSB * 2 + (size_t)2 * 3 * SP * CT * 32 * 2 + (size_t)4 * CT * 2 * sizeof(double);
-  auto kfn = k_c3f<KD, NT, SP, kB6FlatAvMax>;
-  bool use_f16 = false;
-  if constexpr (KD == 3 && SP == 1) {
-    if (options().conv3_b6_pipe != 0) {       // the LDS-DMA software pipeline (its own LDS layout: a zero row per plane, three weight slots)
-      auto kq = k_c3q<NT, kB6FlatAvMax>;
-      kfn = kq;
-      lds = (size_t)3 * (kB6FlatAvMax + 1) * XSB * 2 + (size_t)3 * 3 * CT * 32 * 2 + (size_t)4 * CT * 2 * sizeof(double);
-      if (cd.xamax != nullptr && options().conv3_f16 != 0) {      // two fp16 planes (round 4): the launch carries the input's |max|
-        auto kq2 = k_c3q<NT, kB6FlatAvMax, 2>;
-        kfn = kq2;
-        lds = (size_t)2 * (kB6FlatAvMax + 1) * XSB * 2 + (size_t)3 * 2 * CT * 32 * 2 + (size_t)4 * CT * 2 * sizeof(double);
-        use_f16 = true;
-      }
+static constexpr size_t b6_stat_lds(int CT) { return (size_t)4 * CT * 2 * sizeof(double); }      // statistics scratch [4][CT][2]
+
+// One brick tile configuration: k_c3d (weight fragments straight from global memory) or the staged k_c3b / k_c3h / k_c3p.
+static void b6_route_brick(Conv3Route& r, int KD, int TD, int TH, int TW, int NT, int SP, Conv3Mode mode, int G, bool has_workspace, bool has_amax) {
+  const Options& o = options();
+  ConvDims& cd = r.cd;
+  const int M = TD * TH * TW, CT = NT * 16, PD = KD == 3 ? 1 : 0, HV = (TD + 2 * PD) * (TH + 2) * (TW + 2), T = KD * 9;
+  const bool has_bw = b6_has_bw(KD, TD, TH, TW, NT, SP), has_f16 = b6_has_f16(KD, TD, TH, TW, NT, SP);
+  r.KD = KD; r.TD = TD; r.TH = TH; r.TW = TW; r.NT = NT; r.SP = SP;
+  // k_c3d only where a wave's weight traffic is small next to its MFMAs: 256-voxel tiles with a 32-channel slab (6 KB per 48 MFMAs;
+  // the 64-voxel / 64-channel instances would pull 12 KB per 24 MFMAs through L1: 79-84 vs 47-51 us)
+  const bool direct = o.conv3_b6_direct != 0 && (o.conv3_b6_direct >= 2 || (M == 256 && NT <= 2));
+  const bool pipe64 = b6_is_64x64(TD, TH, TW, NT, SP) && o.conv3_b6_w22 != 0 && o.conv3_b6_pipe != 0;      // -> k_c3p
+  const bool staged2d = KD == 1 && NT == 4;                                                             // -> k_c3b itself
+  // two fp16 planes instead of three bf16 ones: the launch must carry the input's |max| and the instance must exist
+  const bool use_f16 = has_f16 && (staged2d || (NT == 4 ? pipe64 : direct)) && has_amax && o.conv3_f16 != 0;
+  cd.tiles_d = cdiv(cd.D, TD); cd.tiles_h = cdiv(cd.H, TH); cd.tiles_w = cdiv(cd.W, TW);
+  const int gx = cd.N * cd.tiles_d * cd.tiles_h * cd.tiles_w, gy = cd.Cout16 / CT;
+  const bool ws_fits = has_workspace && (long long)cd.N * cd.D * cd.H * cd.W * cd.Cout <= o.conv3_sk_elems;     // bcp_conv3_fwd_workspace_bytes
+  r.sk = ws_fits ? conv3_split_k((long long)gx * gy, cd.Cin16 / 16, false) : 1;
+  const bool stats_ok = r.sk == 1 && G > 0 && gx % G == 0;
+  if (mode == Conv3Mode::bwd_stats) {                 // one-pass launches only
+    if (!has_bw || !stats_ok || (direct && NT == 1)) return;
+    if (o.fuse_bwd_stats == 2 && KD == 3 && NT == 2) return;      // measurement: not at the 3-D 32-channel slabs (k_c3d's epilogue: +39 us per launch)
+    r.bw = true;
+  }
+  r.gx = gx; r.gy = gy; r.tiles = gx;
+  // (raw slabs at 16-channel slabs: the persistent form of k_c3d is not a slab writer; staged kernel)
+  if (direct && !(mode == Conv3Mode::raw && NT == 1)) {
+    // persistent grid (16-channel slabs): tiles dealt round-robin to P workgroups (two per CU), balanced: every workgroup gets
+    // cdiv(tiles, slots) tiles; 32-channel slabs: one tile per workgroup (register budget, see k_c3d) except PT below
+    const bool PER = NT == 1;
+    // PT (option c3d32_form): the 3-D 32-channel slabs on two fp16 planes as persistent workgroups too -- the same balanced deal and XCD walk,
+    // but still ONE STATISTICS ROW PER TILE, so the row count below (and with it every planner's answer) does not depend on the form
+    const bool PT = b6_has_per32(KD, TD, TH, TW, NT, SP) && use_f16 && r.sk == 1 && o.c3d32_form != 0 && mode != Conv3Mode::raw && (!r.bw || b6_per32_bw);
+    r.family = Conv3Family::c3d;
+    r.planes = use_f16 ? 2 : 3;
+    r.persistent = (PER || PT) && mode != Conv3Mode::raw;
+    // the weight fragments of the one cin chunk in the LDS (option c3d16_form): 14 pairs x 2 planes x 1 KB at the 3-D tile,
+    // 68 KB per workgroup with the halo planes -- still two workgroups per CU
+    r.wlds = PER && use_f16 && o.c3d16_form != 0 && cd.Cin16 == 16 && r.sk == 1;
+    r.lds = (size_t)r.planes * HV * XSB * 2 + b6_stat_lds(CT) + (r.wlds ? (size_t)((T + 1) / 2) * 2 * 64 * 16 : 0);
+    if (r.persistent) {
+      const int slots = 512 / (gy * r.sk) > 0 ? 512 / (gy * r.sk) : 1;
+      int P = cdiv(gx, cdiv(gx, slots));
+      if ((cd.xcd & 2) && P >= 8) P = (P + 7) & ~7;             // the XCD-aware walk needs whole rounds of the 8 XCDs
+      if (o.conv3_p > 0 && o.conv3_p < P) P = o.conv3_p;        // tests: few workgroups, many tiles each
+      r.gx = P;
     }
-  }
-  if (!use_f16) cd.xamax = nullptr;
-  g_b6_last_planes = use_f16 ? 2 : 3;
-  if (lds > 48 * 1024) hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int gx = cd.N * tps, gy = cd.Cout16 / CT;
-  const int nch = cd.Cin16 / 16;
-  // split-K over the cin chunks: a deep-level workgroup's life is a serial chain of weight stages (one barrier per tap pair), so the
-  // chain is cut as short as the grid allows -- the largest power of two (<= 8, >= 2 chunks per workgroup) that keeps the launch
-  // within the 512 co-resident workgroup slots; measured alone (fwd + statistics, us): 256 channels batch 2 / 4: 31.3 -> 25.8 /
-  // 40.7 -> 34.3 (with 64-channel slabs at batch 4); 128 channels batch 4: 67.2 -> 59.4 (split 2: 496 workgroups instead of 992)
-  int sk = 1;
-  const bool ws_fits = ws && (long long)cd.N * V * cd.Cout <= options().conv3_sk_elems;
-  if (ws_fits && nch >= 4) {
-    const int cap = nch / 2 < 8 ? nch / 2 : 8;
-    while (sk * 2 <= cap && (long long)gx * gy * sk * 2 <= 512) sk *= 2;
-  }
-  { const int f = options().splitk; if (ws_fits && f >= 1 && f <= 4 && f <= nch) sk = f; }
-  { const int f = options().conv3_b6_flat_sk; if (ws_fits && f >= 1 && f <= 8 && f <= nch) sk = f; }      // measurement override
-  if (raw_sk) {                                       // raw mode: see b6_launch
-    *raw_sk = sk;
-    if (dry) return 0;
-    StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, sk), dim3(256), lds, s, X, Wp, (const float*)nullptr, Y, cd, tps, 0, none);
-    return 0;
-  }
-  if (bw) return 0;                                   // (deep levels: the one-launch norm backward takes the raw slabs instead)
-  StatsArg st{nullptr, 0, 1, cd.Cout, G > 0 ? G : 1};
-  const bool stats_ok = sk == 1 && G > 0 && cd.N % G == 0;        // tiles are sample-major and never straddle samples
-  if (stats_ok) { st.rows = gx / G; st.tiles_per_group = gx / G; st.partial = stat_partial; }
-  if (dry) return stats_ok ? gx / G : 0;
-  if (sk == 1) {
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, 1), dim3(256), lds, s, X, Wp, bias, Y, cd, tps, accumulate, st);
+    if (stats_ok) { r.rows = PER ? (int)r.gx : gx / G; r.tiles_per_group = gx / G; }
   } else {
-    const long long n = (long long)cd.N * V * cd.Cout;
-    StatsArg none{nullptr, 0, 1, cd.Cout, 1};
-    hipLaunchKernelGGL(kfn, dim3(gx, gy, sk), dim3(256), lds, s, X, Wp, (const float*)nullptr, ws, cd, tps, 0, none);
-    hipLaunchKernelGGL(k_b6_sum_slabs, dim3((int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256)), dim3(256), 0, s, ws, sk, n, cd.Cout, bias, Y,
-                       accumulate);
+    r.family = Conv3Family::c3b;
+    r.planes = staged2d && use_f16 ? 2 : 3;           // (k_c3b's only two-plane instance: the U-Net's 64-channel slabs)
+    if (b6_is_64x64(TD, TH, TW, NT, SP) && o.conv3_b6_w22 != 0) {
+      r.family = Conv3Family::c3h;                    // 2 x 2 wave arrangement of the 64 x 64 tile (same LDS layout and size)
+      if (o.conv3_b6_pipe != 0) { r.family = Conv3Family::c3p; r.planes = use_f16 ? 2 : 3; }      // its own LDS layout
+    }
+    // the staged kernels' weight stage is part of their LDS whatever `direct` says.  k_c3p: two halo buffers, three weight slots
+    r.lds = r.family == Conv3Family::c3p ? (size_t)2 * r.planes * HV * XSB * 2 + (size_t)3 * r.planes * 64 * 32 * 2 + b6_stat_lds(32)
+                                         : (size_t)r.planes * HV * XSB * 2 + (size_t)2 * r.planes * SP * CT * 32 * 2 + b6_stat_lds(CT);
+    if (stats_ok) { r.rows = gx / G; r.tiles_per_group = gx / G; }
   }
-  return st.partial ? st.rows : 0;
+  r.served = mode == Conv3Mode::plain || mode == Conv3Mode::raw || r.rows > 0;
 }
 
-// Forward / dgrad on the bf16 pipe where option conv3_b6 allows it.  Returns the statistics rows (as conv3_fwd_impl does);
-// *handled = false leaves the shape to the fp32 kernels.
-int b6_last_planes() { return g_b6_last_planes; }
-
-int b6_fwd(const float* x, const float* wp, const float* bias, float* y, const ConvDims& cd, int KD, int accumulate, void* workspace,
-           double* stat_partial, int G, bool dry, hipStream_t s, bool* handled, int* raw_sk, const BwdStatsIn* bw) {
-  *handled = false;
-  g_b6_last_planes = 3;
+// Flat 64-voxel tiles with per-lane validity masks (deep levels): k_c3f, or its LDS-DMA software pipeline k_c3q
+static void b6_route_flat(Conv3Route& r, int NT, Conv3Mode mode, int G, bool has_workspace, bool has_amax) {
   const Options& o = options();
-  if (o.conv3_b6 == 0) return 0;
+  const ConvDims& cd = r.cd;
+  const int CT = NT * 16, V = cd.D * cd.H * cd.W, tps = cdiv(V, 64);
+  r.KD = 3; r.NT = NT; r.SP = 1;
+  if (mode == Conv3Mode::bwd_stats) return;           // (deep levels: the one-launch norm backward takes the raw slabs instead)
+  if (o.conv3_b6_pipe != 0) {                         // its own LDS layout: a zero row per plane, three weight slots
+    r.family = Conv3Family::c3q;
+    r.planes = has_amax && o.conv3_f16 != 0 ? 2 : 3;  // two fp16 planes (round 4): the launch carries the input's |max|
+    r.lds = (size_t)r.planes * (kB6FlatAvMax + 1) * XSB * 2 + (size_t)3 * r.planes * CT * 32 * 2 + b6_stat_lds(CT);
+  } else {
+    r.family = Conv3Family::c3f;
+    r.planes = 3;
+    r.lds = (size_t)3 * kB6FlatAvMax * XSB * 2 + (size_t)2 * 3 * CT * 32 * 2 + b6_stat_lds(CT);
+  }
+  r.gx = cd.N * tps; r.gy = cd.Cout16 / CT; r.tiles = tps;
+  const bool ws_fits = has_workspace && (long long)cd.N * V * cd.Cout <= o.conv3_sk_elems;
+  r.sk = ws_fits ? conv3_split_k((long long)r.gx * r.gy, cd.Cin16 / 16, true) : 1;
+  if (r.sk == 1 && G > 0 && cd.N % G == 0) { r.rows = r.gx / G; r.tiles_per_group = r.gx / G; }      // tiles are sample-major and never straddle samples
+  r.served = mode == Conv3Mode::plain || mode == Conv3Mode::raw || r.rows > 0;
+}
+
+// Forward / dgrad on the bf16 pipe where option conv3_b6 allows it: fills r (r.cd holds the shape) and returns true, or returns
+// false and leaves the shape to the fp32 kernels.
+bool b6_route(Conv3Route& r, int KD, Conv3Mode mode, int G, bool has_workspace, bool has_amax) {
+  const Options& o = options();
+  const ConvDims& cd = r.cd;
+  if (o.conv3_b6 == 0) return false;
   const long long vox = (long long)cd.N * cd.D * cd.H * cd.W;
-  float* ws = (float*)workspace;
-  int rows = 0;
+  auto brick = [&](int TD, int TH, int TW, int NT, int SP) { b6_route_brick(r, KD, TD, TH, TW, NT, SP, mode, G, has_workspace, has_amax); return true; };
   if (KD == 3) {
     const bool forced = o.conv3_b6 >= 2;
     if (cd.Cout16 == 16 && cd.Cin16 == 16) {
-      if (o.conv3_b6 >= 3 || (o.conv3_b6 == 1 && (o.conv3_b6_levels & 4) && vox >= 256LL * 1024)) {
-        rows = b6_launch<3, 4, 8, 8, 1, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        *handled = true;
-      }
+      if (o.conv3_b6 >= 3 || (o.conv3_b6 == 1 && (o.conv3_b6_levels & 4) && vox >= 256LL * 1024)) return brick(4, 8, 8, 1, 1);
     } else if (cd.Cout16 % 64 == 0) {
       if (forced || ((o.conv3_b6_levels & 2) && vox >= o.conv3_b6_minvox)) {
         // 64-channel slabs.  Mid level (>= 16 K voxels): 64-voxel 4x4x4 tiles -- they tile 28x28x20 exactly and give 490 workgroups
         // (128-voxel tiles: 280 workgroups, one per CU, nothing to overlap with: 66-71 us against 47-51 us).  Deep level
         // (14x14x10, from 2 K voxels): 2x8x4 tiles (37 % padding; 4x8x4 wastes 57 %): 40 us against 52 us for the fp32 kernel, LA step
         // 7.90 against 7.97 ms.  The 7x7x5 level stays with the fp32 kernel (35 vs 32 us).
-        if (vox >= 16LL * 1024) {
-          rows = b6_launch<3, 4, 4, 4, 4, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        } else if (o.conv3_b6_flat && 64 + 2 * (cd.H * cd.W + cd.W + 1) <= kB6FlatAvMax) {
+        if (vox >= 16LL * 1024) return brick(4, 4, 4, 4, 1);
+        if (o.conv3_b6_flat && 64 + 2 * (cd.H * cd.W + cd.W + 1) <= kB6FlatAvMax) {
           // flat 64-voxel tiles; narrower slabs for the smallest volumes (7x7x5: 8 tiles) so that the grid still covers the CUs at the
-          // split-K the launcher picks
+          // split-K the route picks
           const long long gx8 = (long long)cd.N * cdiv(cd.D * cd.H * cd.W, 64) * (cd.Cout16 / 64) * 8;     // workgroups with 64-channel slabs at split 8
           const int nt = o.conv3_b6_flat >= 2 ? (o.conv3_b6_flat == 2 ? 2 : (o.conv3_b6_flat == 4 ? 4 : 1))
                                               : ((vox >= 2048 || (cd.Cin16 >= 256 && gx8 >= 512)) ? 4 : 2);
-          if (nt == 4) rows = b6_launch_flat<3, 4, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-          else if (nt == 2) rows = b6_launch_flat<3, 2, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-          else rows = b6_launch_flat<3, 1, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        } else {
-          rows = b6_launch<3, 2, 8, 4, 4, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
+          b6_route_flat(r, nt, mode, G, has_workspace, has_amax);
+          return true;
         }
-        *handled = true;
+        return brick(2, 8, 4, 4, 1);
       }
     } else if (cd.Cout16 % 32 == 0) {
-      if (forced || ((o.conv3_b6_levels & 1) && vox >= o.conv3_b6_minvox)) {
-        if (vox >= 64LL * 1024 || cd.W % 8 == 0) rows = b6_launch<3, 4, 8, 8, 2, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        else rows = b6_launch<3, 4, 4, 8, 2, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        *handled = true;
-      }
+      if (forced || ((o.conv3_b6_levels & 1) && vox >= o.conv3_b6_minvox))
+        return vox >= 64LL * 1024 || cd.W % 8 == 0 ? brick(4, 8, 8, 2, 1) : brick(4, 4, 8, 2, 1);
     }
   } else {
     // 2-D (U-Net): ACDC step 5.18 -> 4.24 ms with the 32- to 256-channel levels (and their weight gradients) on the bf16 pipe
@@ -2036,24 +1876,102 @@ int b6_fwd(const float* x, const float* wp, const float* bias, float* y, const C
     if (cd.Cout16 == 16 && cd.Cin16 <= o.conv3_b6_cin16max) {
       // the U-Net's 16-channel layers at full resolution (16 -> 16 and, after the skip concatenation, 32 -> 16): 16x16 tiles on the
       // persistent direct-weight kernel, as the 3-D 16-channel level (work items = (tile, cin chunk))
-      if (o.conv3_b6 >= 3 || (o.conv3_b6 == 1 && (o.conv3_b6_levels & 8) && (o.conv3_b6_levels & 4) && vox >= 256LL * 1024)) {
-        rows = b6_launch<1, 1, 16, 16, 1, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-        *handled = true;
-      }
+      if (o.conv3_b6 >= 3 || (o.conv3_b6 == 1 && (o.conv3_b6_levels & 8) && (o.conv3_b6_levels & 4) && vox >= 256LL * 1024)) return brick(1, 16, 16, 1, 1);
     } else if (cd.Cout16 % 64 == 0 && on) {
       // (flat 64-pixel tiles, k_c3f<1,..>, lose here: ACDC step 4.28 / 4.44 vs 4.14 ms for the levels up to 16 K / 64 K pixels)
-      rows = b6_launch<1, 1, 8, 16, 4, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-      *handled = true;
+      return brick(1, 8, 16, 4, 1);
     } else if (cd.Cout16 % 32 == 0 && on) {
       // 32-channel slabs: from 64 K pixels on 16x16 tiles with direct weight fragments (k_c3d, as the 3-D 32-channel level) -- the
       // staged 8x16 kernel ran the 16 -> 32 dgrad at 256x256 at 54 TFLOP/s-eq; ACDC step 4.11 -> 4.05 ms (cfg2d: 0 staged, 2 always direct)
-      if (o.conv3_b6_cfg2d >= 2 || (o.conv3_b6_cfg2d == 1 && vox >= 64LL * 1024))
-        rows = b6_launch<1, 1, 16, 16, 2, 1>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-      else rows = b6_launch<1, 1, 8, 16, 2, 2>(x, wp, bias, y, cd, accumulate, ws, stat_partial, G, dry, s, raw_sk, bw);
-      *handled = true;
+      return o.conv3_b6_cfg2d >= 2 || (o.conv3_b6_cfg2d == 1 && vox >= 64LL * 1024) ? brick(1, 16, 16, 2, 1) : brick(1, 8, 16, 2, 2);
     }
   }
-  return rows;
+  return false;
+}
+
+// ---- the record -> the kernel instance.  Every instance of a tile configuration is named here once; nullptr: no such instance.
+template <int KD, int TD, int TH, int TW, int NT, int SP>
+static Conv3KernelT c3d_instance(bool per, bool bw, bool f16, bool wlds) {
+  constexpr bool HB = b6_has_bw(KD, TD, TH, TW, NT, SP), HF = b6_has_f16(KD, TD, TH, TW, NT, SP), HP = b6_has_per32(KD, TD, TH, TW, NT, SP), PER = NT == 1;
+  if (wlds) {
+    if constexpr (PER && HF) { if (per && !bw && f16) return k_c3d<KD, TD, TH, TW, NT, true, false, 2, true>; }
+    return nullptr;
+  }
+  if (!per) {                                         // one tile per workgroup
+    if (!bw && !f16) return k_c3d<KD, TD, TH, TW, NT, false>;
+    if constexpr (HF) { if (!bw) return k_c3d<KD, TD, TH, TW, NT, false, false, 2>; }
+    if constexpr (HB && !PER) { if (bw && !f16) return k_c3d<KD, TD, TH, TW, NT, false, true>; }
+    if constexpr (HB && !PER && HF) { if (bw) return k_c3d<KD, TD, TH, TW, NT, false, true, 2>; }
+    return nullptr;
+  }
+  if constexpr (PER) {
+    if (!bw && !f16) return k_c3d<KD, TD, TH, TW, NT, true>;
+    if constexpr (HF) { if (!bw) return k_c3d<KD, TD, TH, TW, NT, true, false, 2>; }
+  }
+  if constexpr (HP) {
+    if (!bw && f16) return k_c3d<KD, TD, TH, TW, NT, true, false, 2>;
+    if constexpr (HB && b6_per32_bw) { if (f16) return k_c3d<KD, TD, TH, TW, NT, true, true, 2>; }
+  }
+  return nullptr;
+}
+
+template <int KD, int TD, int TH, int TW, int NT, int SP>
+static Conv3Kernel b6_instance(const Conv3Route& r) {
+  constexpr bool HB = b6_has_bw(KD, TD, TH, TW, NT, SP), HF = b6_has_f16(KD, TD, TH, TW, NT, SP);
+  const bool bw = r.bw, f16 = r.planes == 2;
+  Conv3Kernel k;
+  if (r.family == Conv3Family::c3d) k.t = c3d_instance<KD, TD, TH, TW, NT, SP>(r.persistent, bw, f16, r.wlds);
+  if (r.family == Conv3Family::c3b) {
+    if (!bw && !f16) k.a = k_c3b<KD, TD, TH, TW, NT, SP>;
+    if constexpr (HB) { if (bw && !f16) k.a = k_c3b<KD, TD, TH, TW, NT, SP, true>; }
+    if constexpr (KD == 1 && NT == 4 && HF) { if (!bw && f16) k.a = k_c3b<KD, TD, TH, TW, NT, SP, false, 2>; }      // the U-Net's 64-channel slabs on two fp16 planes
+  }
+  if constexpr (b6_is_64x64(TD, TH, TW, NT, SP)) {
+    if (r.family == Conv3Family::c3h && !f16) {
+      if (!bw) k.a = k_c3h<KD, TD, TH, TW>;
+      if constexpr (HB) { if (bw) k.a = k_c3h<KD, TD, TH, TW, true>; }
+    }
+    if (r.family == Conv3Family::c3p) {
+      if (!bw && !f16) k.a = k_c3p<KD, TD, TH, TW>;
+      if constexpr (HB) { if (bw && !f16) k.a = k_c3p<KD, TD, TH, TW, true>; }
+      if constexpr (HF) { if (!bw && f16) k.a = k_c3p<KD, TD, TH, TW, false, 2>; }
+      if constexpr (HB && HF) { if (bw && f16) k.a = k_c3p<KD, TD, TH, TW, true, 2>; }
+    }
+  }
+  return k;
+}
+
+template <int NT>
+static Conv3Kernel b6_flat_instance(const Conv3Route& r) {
+  Conv3Kernel k;
+  if (r.bw) return k;
+  if (r.family == Conv3Family::c3f && r.planes == 3) k.t = k_c3f<3, NT, 1, kB6FlatAvMax>;
+  if (r.family == Conv3Family::c3q) k.t = r.planes == 2 ? k_c3q<NT, kB6FlatAvMax, 2> : k_c3q<NT, kB6FlatAvMax>;
+  return k;
+}
+
+static constexpr int b6_tile_key(int KD, int TD, int TH, int TW, int NT, int SP) { return ((((KD * 32 + TD) * 32 + TH) * 32 + TW) * 8 + NT) * 4 + SP; }
+
+Conv3Kernel b6_kernel(const Conv3Route& r) {
+  Conv3Kernel k;
+  if (r.family == Conv3Family::c3f || r.family == Conv3Family::c3q) {
+    k = r.NT == 4 ? b6_flat_instance<4>(r) : r.NT == 2 ? b6_flat_instance<2>(r) : r.NT == 1 ? b6_flat_instance<1>(r) : k;
+  } else {
+    switch (b6_tile_key(r.KD, r.TD, r.TH, r.TW, r.NT, r.SP)) {
+      case b6_tile_key(3, 4, 8, 8, 1, 1): k = b6_instance<3, 4, 8, 8, 1, 1>(r); break;
+      case b6_tile_key(3, 4, 4, 4, 4, 1): k = b6_instance<3, 4, 4, 4, 4, 1>(r); break;
+      case b6_tile_key(3, 2, 8, 4, 4, 1): k = b6_instance<3, 2, 8, 4, 4, 1>(r); break;
+      case b6_tile_key(3, 4, 8, 8, 2, 1): k = b6_instance<3, 4, 8, 8, 2, 1>(r); break;
+      case b6_tile_key(3, 4, 4, 8, 2, 1): k = b6_instance<3, 4, 4, 8, 2, 1>(r); break;
+      case b6_tile_key(1, 1, 16, 16, 1, 1): k = b6_instance<1, 1, 16, 16, 1, 1>(r); break;
+      case b6_tile_key(1, 1, 8, 16, 4, 1): k = b6_instance<1, 1, 8, 16, 4, 1>(r); break;
+      case b6_tile_key(1, 1, 16, 16, 2, 1): k = b6_instance<1, 1, 16, 16, 2, 1>(r); break;
+      case b6_tile_key(1, 1, 8, 16, 2, 2): k = b6_instance<1, 1, 8, 16, 2, 2>(r); break;
+    }
+  }
+  k.sum = k_b6_sum_slabs;
+  return k;
 }
 
 }  // namespace bcp
+

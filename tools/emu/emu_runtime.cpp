@@ -3,7 +3,10 @@
 #include <hip/hip_runtime.h>
 
 #include <condition_variable>
+#include <cxxabi.h>
+#include <dlfcn.h>
 #include <mutex>
+#include <string>
 
 extern "C" void bcpemu_switch(void** save_sp, void* load_sp);
 asm(R"(
@@ -331,4 +334,48 @@ void run_grid(dim3 grid, dim3 block, size_t shmem, const std::function<void()>& 
   }
 }
 
+// ---------------- launch log (see hip_runtime.h)
+static std::mutex g_log_mu;
+static std::string g_log;
+static std::atomic<int> g_log_mode{0};
+
+static std::string symbol_of(const void* fn) {
+  Dl_info info;
+  if (!dladdr(fn, &info) || !info.dli_sname) return "?";
+  int status = 0;
+  char* d = abi::__cxa_demangle(info.dli_sname, nullptr, nullptr, &status);
+  std::string name = status == 0 && d ? d : info.dli_sname;
+  free(d);
+  const size_t paren = name.find('(');          // kernel name with its template arguments; the parameter list adds nothing
+  if (paren != std::string::npos) name.resize(paren);
+  if (name.compare(0, 5, "void ") == 0) name.erase(0, 5);
+  return name;
+}
+
+bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem) {
+  const int mode = g_log_mode.load();
+  if (mode == 0) return true;
+  char tail[128];
+  snprintf(tail, sizeof tail, "|%u,%u,%u|%u,%u,%u|%zu\n", gx, gy, gz, bx, by, bz, shmem);
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  g_log += "L|" + symbol_of(fn) + tail;
+  return mode != 2;
+}
+
+void note_attr(const void* fn, int value) {
+  if (g_log_mode.load() == 0) return;
+  std::lock_guard<std::mutex> lk(g_log_mu);
+  g_log += "A|" + symbol_of(fn) + "|" + std::to_string(value) + "\n";
+}
+
 }  // namespace bcpemu
+
+// test-only exports (not part of the product library's ABI): set the log mode; copy the log out (NUL-terminated) and clear it.
+// bcpemu_log_take returns the bytes the whole log needs; with a smaller cap nothing is copied or cleared.
+extern "C" int bcpemu_log_mode(int mode) { return bcpemu::g_log_mode.exchange(mode); }
+extern "C" long bcpemu_log_take(char* buf, long cap) {
+  std::lock_guard<std::mutex> lk(bcpemu::g_log_mu);
+  const long need = (long)bcpemu::g_log.size() + 1;
+  if (buf && cap >= need) { memcpy(buf, bcpemu::g_log.c_str(), need); bcpemu::g_log.clear(); }
+  return need;
+}

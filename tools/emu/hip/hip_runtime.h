@@ -58,7 +58,13 @@ inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind
 inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
-template <class F> inline hipError_t hipFuncSetAttribute(F, hipFuncAttribute, int) { return hipSuccess; }
+// launch log (tests/test_emu_conv3_routes.py): mode 0 = off, 1 = note every launch and attribute call, 2 = note them and do not execute
+// the launches (entry points may then be handed any non-null aligned buffer).  Read through bcpemu_log_take (emu_runtime.cpp).
+namespace bcpemu {
+bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem);   // false: do not execute
+void note_attr(const void* fn, int value);
+}
+template <class F> inline hipError_t hipFuncSetAttribute(F f, hipFuncAttribute, int v) { ::bcpemu::note_attr((const void*)f, v); return hipSuccess; }
 struct hipDeviceProp_t { char gcnArchName[256]; int multiProcessorCount; };
 inline hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { strcpy(p->gcnArchName, "emu-x86"); p->multiProcessorCount = 8; return hipSuccess; }
@@ -307,6 +313,7 @@ using std::min;
 // ---- launch
 template <class K, class... Args>
 inline void bcpemu_launch(K kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
+  if (!::bcpemu::note_launch((const void*)kernel, grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem)) return;
   std::function<void()> body = [=]() { kernel(args...); };
   ::bcpemu::run_grid(grid, block, shmem, body);
 }
