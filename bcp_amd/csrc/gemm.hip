@@ -11,6 +11,7 @@
 // TN kernel:  P[k][n] = sum_m A(m, k) * B(m, n)                (weight gradients; M = voxels)
 // Both use v_mfma_f32_16x16x4_f32; lane (i = l&15, g = l>>4).
 #include "common.h"
+#include "norm_shared.h"
 #include <cstring>
 #include <cstdlib>
 #include "../../include/bcp_hip.h"
@@ -854,122 +855,12 @@ __global__ void k_colsum_finalize(const double* __restrict__ accum, float* __res
   if (i < C) out[i] = (accumulate ? out[i] : 0.f) + (float)accum[i];
 }
 
-static RowMap make_map(const float* p, int mode, int L, int Cs, int D, int H, int W) {
-  RowMap m;
+// ---- Host dispatch: one problem record (k2_problem), one route (gemm_route / tn_route: pure functions of the problem, the requested epilogue
+// and options()), one launcher (nn_launch / tn_launch: one table of kernel instances each).  Pinned by tests/test_emu_gemm_routes.py.
+static RowMap make_map(RowMap m, const float* p) {      // the problem's maps carry no pointer: a launch adds it
   m.p = const_cast<float*>(p);
-  m.mode = mode; m.L = L; m.Cs = Cs; m.D = D; m.H = H; m.W = W;
   return m;
 }
-
-static int pick_nt(int N, long long row_blocks) {
-  int nt = 4;
-  while (nt > 1 && (N % (nt * 16) != 0)) nt >>= 1;
-  while (nt > 1 && row_blocks * (N / (nt * 16)) < 256) nt >>= 1;
-  return nt;
-}
-
-static int launch_nn(RowMap A, const float* Bp, const float* bias, RowMap C, int M, int K, int N, int bias_mod, int accumulate,
-                     hipStream_t s) {
-  const int rb = cdiv(M, 64);
-  const int nt = pick_nt(N, rb);
-  const dim3 grid(rb, N / (nt * 16));
-  const GemmStats none{nullptr, 0, 0, 0, 0, 0, nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, 0};
-  // (round 6, option gemm_walk = W > 0) launches of >= 2 W workgroups as ~W workgroups that walk R <= 16 row blocks each with the next block's
-  // operands in flight (k_gemm_nn<.., 7>: the statistics instances' walk without their epilogue)
-  const int walk = options().gemm_walk;
-  if (walk > 0 && (long long)rb * grid.y >= 2LL * walk) {
-    int R = cdiv((long long)rb * grid.y, walk);
-    if (R > 16) R = 16;
-    GemmStats st = none;
-    st.R = R;
-    st.pipe = options().gemm_pipe;
-    const dim3 g2(cdiv(rb, R), grid.y);
-    if (nt == 4) hipLaunchKernelGGL((k_gemm_nn<4, 7>), g2, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-    else if (nt == 2) hipLaunchKernelGGL((k_gemm_nn<2, 7>), g2, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-    else hipLaunchKernelGGL((k_gemm_nn<1, 7>), g2, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-    return 0;
-  }
-  if (nt == 4) hipLaunchKernelGGL((k_gemm_nn<4>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, none);
-  else if (nt == 2) hipLaunchKernelGGL((k_gemm_nn<2>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, none);
-  else hipLaunchKernelGGL((k_gemm_nn<1>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, none);
-  return 0;
-}
-
-// the statistics variant's geometry: 64-row blocks per workgroup R, partial rows per group; false: not served (the norm's own pass runs)
-struct StatPlan { int nt, R, wpg, ysets, nb; };
-static bool stat_plan(StatPlan& p, int M, int N, int Cout, int groups) {
-  if (groups < 1 || M % groups) return false;
-  const int mpg = M / groups;
-  if (mpg % 64) return false;                       // a 64-row block must not straddle two normalisation groups
-  const int bpg = mpg / 64;
-  p.nt = pick_nt(N, (long long)bpg * groups);
-  const int CT = p.nt * 16;
-  if (Cout % 16 || (Cout < CT && CT % Cout) || (Cout > CT && Cout % CT) || N % Cout) return false;
-  const int gy = N / CT, ychan = Cout > CT ? Cout / CT : 1;
-  p.ysets = gy / ychan;
-  // as many row blocks per workgroup as keep <= ~1024 partial rows per group and >= 512 workgroups in the launch
-  int R = 1;
-  while (R < 16 && bpg % (R * 2) == 0 && ((long long)(bpg / R) * p.ysets > 1024) && (long long)(bpg / (R * 2)) * groups * gy >= 512) R *= 2;
-  { const int v = options().gemm_stat_r; if (v > 0 && v <= 16 && bpg % v == 0) R = v; }      // measurement switch
-  p.R = R;
-  p.wpg = bpg / R;
-  p.nb = p.wpg * p.ysets;
-  return true;
-}
-
-template <int MODE>
-static int launch_nn_mode(RowMap A, const float* Bp, const float* bias, RowMap C, int M, int K, int N, int Cch, int bias_mod, int accumulate,
-                          double* partial, int groups, const float* by, const float* bstats, int act, const float* aux, const float* c1c2, float* amax,
-                          hipStream_t s) {
-  StatPlan p;
-  if (!stat_plan(p, M, N, Cch, groups)) return 0;
-  const dim3 grid(p.wpg * groups, N / (p.nt * 16));
-  const GemmStats st{partial, p.nb, Cch, p.wpg, p.R, p.ysets, by, bstats, groups, act, aux, c1c2, amax, options().gemm_pipe};
-  if (p.nt == 4) hipLaunchKernelGGL((k_gemm_nn<4, MODE>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-  else if (p.nt == 2) hipLaunchKernelGGL((k_gemm_nn<2, MODE>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-  else hipLaunchKernelGGL((k_gemm_nn<1, MODE>), grid, dim3(256), 0, s, A, Bp, bias, C, M, K, N, bias_mod, accumulate, st);
-  return p.nb;
-}
-
-static int launch_nn_stats(RowMap A, const float* Bp, const float* bias, RowMap C, int M, int K, int N, int Cch, int bias_mod, int accumulate,
-                           double* partial, int groups, const float* by, const float* bstats, int act, hipStream_t s) {
-  if (by) return launch_nn_mode<2>(A, Bp, bias, C, M, K, N, Cch, bias_mod, accumulate, partial, groups, by, bstats, act, nullptr, nullptr, nullptr, s);
-  return launch_nn_mode<1>(A, Bp, bias, C, M, K, N, Cch, bias_mod, accumulate, partial, groups, nullptr, nullptr, 0, nullptr, nullptr, nullptr, s);
-}
-
-static int tn_groups(int M, int K, int N, int nt) {
-  const int chan_blocks = cdiv(K, 64) * (N / (nt * 16));
-  int g = cdiv(512, chan_blocks);
-  const int max_g = cdiv(M, 64);
-  { const int v = options().tn_groups; if (v > 0 && v < g) g = v; }   // tests: force multi-chunk groups
-  if (g > max_g) g = max_g;
-  if (g < 1) g = 1;
-  return g;
-}
-static int tn_nt(int N) {
-  int nt = 4;
-  while (nt > 1 && (N % (nt * 16) != 0)) nt >>= 1;
-  return nt;
-}
-
-static int launch_tn(RowMap A, RowMap B, float* partial, float* out, int M, int K, int N, Idx4 ix, int accumulate, hipStream_t s) {
-  const int nt = tn_nt(N);
-  const int g0 = tn_groups(M, K, N, nt);
-  const int rpg = cdiv(cdiv(M, g0), 64) * 64;
-  const int G = cdiv(M, rpg);
-  const dim3 grid(G, cdiv(K, 64), N / (nt * 16));
-  if (nt == 4) hipLaunchKernelGGL((k_gemm_tn<4>), grid, dim3(256), 0, s, A, B, partial, M, K, N, rpg);
-  else if (nt == 2) hipLaunchKernelGGL((k_gemm_tn<2>), grid, dim3(256), 0, s, A, B, partial, M, K, N, rpg);
-  else hipLaunchKernelGGL((k_gemm_tn<1>), grid, dim3(256), 0, s, A, B, partial, M, K, N, rpg);
-  const long long total = (long long)K * N;
-  hipLaunchKernelGGL(k_tn_reduce, dim3((int)((total + 15) / 16 > 4096 ? 4096 : (total + 15) / 16)), dim3(256), 0, s, partial,
-                     out, G, K, N, ix, accumulate);
-  return 0;
-}
-
-}  // namespace bcp
-
-using namespace bcp;
 
 // kind: which GEMM the packed matrix feeds (see include/bcp_hip.h)
 static int k2_pack_geometry(int Cin, int Cout, int kind, int& K, int& N, Idx4& ix) {
@@ -990,6 +881,176 @@ static int k2_pack_geometry(int Cin, int Cout, int kind, int& K, int& N, Idx4& i
   }
   return 0;
 }
+
+// The five GEMMs of the family; an op IS the pack kind of the weight matrix it reads.  The weight gradient of a layer is the TN GEMM over
+// its forward op's record: the same two row maps (x side, dy side), the same K x N, and the pack geometry's Idx4 run backwards.
+enum K2Op { K2_DOWN_FWD = BCP_PACK_DOWN_FWD, K2_DOWN_DGRAD = BCP_PACK_DOWN_DGRAD, K2_UP_FWD = BCP_PACK_UP_FWD, K2_UP_DGRAD = BCP_PACK_UP_DGRAD,
+            K2_PW_FWD = BCP_PACK_PW_FWD };
+struct K2Problem {
+  long long M;           // rows: coarse voxels N * D/2 * H/2 * W/2 ((D, H, W) the FINE dims); pointwise: N * D * H * W
+  int K, N;
+  RowMap a, c;           // (p = nullptr) NN: operand A and output C.  TN: the x-side and the dy-side operand
+  int Cch;               // NN: channels of the output -- the statistics epilogues fold the N columns onto them
+  int bias_mod;          // NN: bias[n % bias_mod]
+  Idx4 ix;               // TN: where P[k][n] lands in dw
+};
+
+// The one shape check.  The entry points ask for even extents and channel multiples of 16 (nothing about N, and 0 passes as even); the
+// row-count queries (strict) also for N >= 1, extents >= 2 and channels >= 16, and answer 0 rows otherwise.
+static bool k2_shape_ok(bool strict, int N, int D, int H, int W, int Cin, int Cout) {
+  if ((D | H | W) & 1 || Cin % 16 || Cout % 16) return false;
+  return !strict || (N >= 1 && D >= 2 && H >= 2 && W >= 2 && Cin >= 16 && Cout >= 16);
+}
+
+static K2Problem k2_problem(K2Op op, int N, int D, int H, int W, int Cin, int Cout) {
+  const RowMap fine_in{nullptr, MAP_PATCH, 8 * Cin, Cin, D, H, W}, fine_out{nullptr, MAP_PATCH, 8 * Cout, Cout, D, H, W};
+  const RowMap rows_in{nullptr, MAP_PLAIN, Cin, 0, 0, 0, 0}, rows_out{nullptr, MAP_PLAIN, Cout, 0, 0, 0, 0};
+  K2Problem p{};
+  p.M = op == K2_PW_FWD ? (long long)N * D * H * W : N * (D / 2) * (H / 2) * (W / 2);
+  if (k2_pack_geometry(Cin, Cout, op, p.K, p.N, p.ix) != 0) abort();      // an op without a pack kind: a programming error
+  switch (op) {
+    case K2_DOWN_FWD:   p.a = fine_in;  p.c = rows_out; p.Cch = Cout; p.bias_mod = Cout; break;      // y[coarse][Cout] = gather(x fine) * B + bias
+    case K2_DOWN_DGRAD: p.a = rows_out; p.c = fine_in;  p.Cch = Cin;  p.bias_mod = 1;    break;      // dx fine (+)= scatter(dy[coarse][Cout] * B')
+    case K2_UP_FWD:     p.a = rows_in;  p.c = fine_out; p.Cch = Cout; p.bias_mod = Cout; break;      // y fine = scatter(x[coarse][Cin] * B) + bias
+    case K2_UP_DGRAD:   p.a = fine_out; p.c = rows_in;  p.Cch = Cin;  p.bias_mod = 1;    break;      // dx[coarse][Cin] (+)= gather(dy fine) * B'
+    case K2_PW_FWD:     p.a = rows_in;  p.c = rows_out; p.Cch = Cout; p.bias_mod = Cout; break;      // y[rows][Cout] = x[rows][Cin] * B + bias
+    default: abort();      // a sixth op gets its arm here
+  }
+  return p;
+}
+
+// ---- the NN route.  The requested epilogue is the kernel's MODE, but for EPI_NONE, which option gemm_walk can send to MODE_WALK.
+enum { EPI_NONE = 0, EPI_FWD_STATS = 1, EPI_BWD_STATS = 2, EPI_RC_FWD_STATS = 3, EPI_RC_FWD_APPLY = 4, EPI_RC_BWD_STATS = 5, EPI_RC_BWD_APPLY = 6,
+       MODE_WALK = 7 };
+struct GemmRoute {
+  bool served;           // false: the statistics / recompute epilogue does not serve this shape (the norm's own pass runs); nb is 0 then
+  int nt, mode;          // kNnKernels[mode][nt >> 1]
+  dim3 grid;
+  int R, wpg, ysets, nb, pipe, G;         // GemmStats: 64-row blocks per workgroup, workgroup x-indices / partial rows per group, .., groups
+};
+
+static int widest_nt(int N) {
+  int nt = 4;
+  while (nt > 1 && (N % (nt * 16) != 0)) nt >>= 1;
+  return nt;
+}
+static int pick_nt(int N, long long row_blocks) {
+  int nt = widest_nt(N);
+  while (nt > 1 && row_blocks * (N / (nt * 16)) < 256) nt >>= 1;
+  return nt;
+}
+
+static GemmRoute gemm_route(const K2Problem& p, int epi, int groups) {
+  GemmRoute r{};
+  const int M = (int)p.M, N = p.N;
+  if (epi == EPI_NONE) {
+    const int rb = cdiv(M, 64);
+    r.served = true;
+    r.nt = pick_nt(N, rb);
+    r.grid = dim3(rb, N / (r.nt * 16));
+    // (round 6, option gemm_walk = W > 0) launches of >= 2 W workgroups as ~W workgroups that walk R <= 16 row blocks each with the next block's
+    // operands in flight (k_gemm_nn<.., 7>: the statistics instances' walk without their epilogue)
+    const int walk = options().gemm_walk;
+    if (walk > 0 && (long long)rb * r.grid.y >= 2LL * walk) {
+      r.mode = MODE_WALK;
+      r.R = cdiv((long long)rb * r.grid.y, walk);
+      if (r.R > 16) r.R = 16;
+      r.pipe = options().gemm_pipe;
+      r.grid.x = cdiv(rb, r.R);
+    }
+    return r;
+  }
+  // the statistics variants' geometry: R 64-row blocks per workgroup, nb partial rows per group
+  if (groups < 1 || M % groups) return r;
+  const int mpg = M / groups;
+  if (mpg % 64) return r;                           // a 64-row block must not straddle two normalisation groups
+  const int bpg = mpg / 64, Cch = p.Cch;
+  r.nt = pick_nt(N, (long long)bpg * groups);
+  const int CT = r.nt * 16;
+  if (Cch % 16 || (Cch < CT && CT % Cch) || (Cch > CT && Cch % CT) || N % Cch) return r;
+  const int gy = N / CT, ychan = Cch > CT ? Cch / CT : 1;
+  const int ysets = gy / ychan;
+  // as many row blocks per workgroup as keep <= ~1024 partial rows per group and >= 512 workgroups in the launch
+  int R = 1;
+  while (R < 16 && bpg % (R * 2) == 0 && ((long long)(bpg / R) * ysets > 1024) && (long long)(bpg / (R * 2)) * groups * gy >= 512) R *= 2;
+  { const int v = options().gemm_stat_r; if (v > 0 && v <= 16 && bpg % v == 0) R = v; }      // measurement switch
+  r.mode = epi;
+  r.R = R; r.wpg = bpg / R; r.ysets = ysets; r.nb = r.wpg * ysets;
+  r.pipe = options().gemm_pipe; r.G = groups;
+  r.grid = dim3(r.wpg * groups, gy);
+  r.served = r.nb > 0;
+  return r;
+}
+
+// ... under an option that gates the epilogue: 0 = off, 2 = only where the output has >= min_elems elements, else wherever the shape is served
+static GemmRoute gated_route(int option, long long min_elems, const K2Problem& p, int epi, int groups) {
+  if (option == 0 || (option == 2 && p.M * p.N < min_elems)) return GemmRoute{};
+  return gemm_route(p, epi, groups);
+}
+
+// what a launch adds to the problem: the operands, and what the epilogues of modes 1 .. 6 read and write (GemmStats)
+struct GemmArgs {
+  const float* a; const float* bp; const float* bias; float* c;
+  int accumulate;
+  double* partial = nullptr;
+  const float* by = nullptr; const float* bstats = nullptr;
+  int act = 0;
+  const float* aux = nullptr; const float* c1c2 = nullptr;
+  float* amax = nullptr;
+};
+
+typedef void (*GemmNnKernel)(RowMap, const float*, const float*, RowMap, int, int, int, int, int, GemmStats);
+#define BCP_NN_ROW(MODE) {k_gemm_nn<1, MODE>, k_gemm_nn<2, MODE>, k_gemm_nn<4, MODE>}
+static const GemmNnKernel kNnKernels[8][3] = {BCP_NN_ROW(0), BCP_NN_ROW(1), BCP_NN_ROW(2), BCP_NN_ROW(3), BCP_NN_ROW(4), BCP_NN_ROW(5), BCP_NN_ROW(6), BCP_NN_ROW(7)};
+#undef BCP_NN_ROW
+
+static void nn_launch(const GemmRoute& r, const K2Problem& p, const GemmArgs& g, hipStream_t s) {
+  const GemmStats st{g.partial, r.nb, r.G ? p.Cch : 0, r.wpg, r.R, r.ysets, g.by, g.bstats, r.G, g.act, g.aux, g.c1c2, g.amax, r.pipe};
+  hipLaunchKernelGGL(kNnKernels[r.mode][r.nt >> 1], r.grid, dim3(256), 0, s, make_map(p.a, g.a), g.bp, g.bias, make_map(p.c, g.c), (int)p.M, p.K, p.N,
+                     p.bias_mod, g.accumulate, st);
+}
+
+// the body of the nine single-GEMM entry points: route, refuse what the route does not serve, launch
+static int nn_entry(const char* who, const K2Problem& p, int epi, int groups, const GemmArgs& g, void* stream) {
+  const GemmRoute r = gemm_route(p, epi, groups);
+  BCP_REQUIRE(r.served, "%s: fused statistics unavailable for this shape (check %s first)", who,
+              epi == EPI_FWD_STATS ? "bcp_k2_stat_rows" : "bcp_k2_bwdstat_rows");
+  nn_launch(r, p, g, (hipStream_t)stream);
+  BCP_CHECK_LAUNCH(who);
+  return BCP_OK;
+}
+
+// ---- the TN route (weight gradients): G groups of rpg rows each leave a K x N partial, k_tn_reduce sums them into dw
+struct TnRoute { int nt, G, rpg; dim3 grid; };
+static TnRoute tn_route(long long M, int K, int N) {
+  TnRoute r;
+  r.nt = widest_nt(N);
+  const int chan_blocks = cdiv(K, 64) * (N / (r.nt * 16));
+  int g = cdiv(512, chan_blocks);
+  const int max_g = cdiv((int)M, 64);
+  { const int v = options().tn_groups; if (v > 0 && v < g) g = v; }   // tests: force multi-chunk groups
+  if (g > max_g) g = max_g;
+  if (g < 1) g = 1;
+  r.rpg = cdiv(cdiv(M, g), 64) * 64;
+  r.G = cdiv(M, r.rpg);
+  r.grid = dim3(r.G, cdiv(K, 64), N / (r.nt * 16));
+  return r;
+}
+
+typedef void (*GemmTnKernel)(RowMap, RowMap, float*, int, int, int, int);
+static const GemmTnKernel kTnKernels[3] = {k_gemm_tn<1>, k_gemm_tn<2>, k_gemm_tn<4>};
+
+static void tn_launch(const K2Problem& p, const float* x, const float* dy, float* partial, float* dw, int accumulate, hipStream_t s) {
+  const TnRoute r = tn_route(p.M, p.K, p.N);
+  hipLaunchKernelGGL(kTnKernels[r.nt >> 1], r.grid, dim3(256), 0, s, make_map(p.a, x), make_map(p.c, dy), partial, (int)p.M, p.K, p.N, r.rpg);
+  const long long total = (long long)p.K * p.N;
+  hipLaunchKernelGGL(k_tn_reduce, dim3((int)((total + 15) / 16 > 4096 ? 4096 : (total + 15) / 16)), dim3(256), 0, s, partial, dw, r.G, p.K, p.N,
+                     p.ix, accumulate);
+}
+
+}  // namespace bcp
+
+using namespace bcp;
 
 // kind: which GEMM the packed matrix feeds (see include/bcp_hip.h)
 extern "C" int bcp_k2_pack_weight(const float* w, float* bp, int Cin, int Cout, int kind, void* stream) {
@@ -1027,77 +1088,72 @@ extern "C" int bcp_k2_pack_many(const void* descs_dev, int n, void* stream) {
   return BCP_OK;
 }
 
+// ---- the plain entry points; (D, H, W) are the FINE dims everywhere
+
 // Down conv forward:  y[coarse][Cout] = gather(x fine [N][D][H][W][Cin]) * B + bias
 extern "C" int bcp_down_fwd(const float* x, const float* bp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
                             int Cout, void* stream) {
   BCP_REQUIRE(x && bp && y, "bcp_down_fwd: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_down_fwd: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  launch_nn(make_map(x, MAP_PATCH, 8 * Cin, Cin, D, H, W), bp, bias, make_map(y, MAP_PLAIN, Cout, 0, 0, 0, 0), M, 8 * Cin, Cout,
-            Cout, 0, (hipStream_t)stream);
-  BCP_CHECK_LAUNCH("bcp_down_fwd");
-  return BCP_OK;
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_down_fwd: bad shape");
+  return nn_entry("bcp_down_fwd", k2_problem(K2_DOWN_FWD, N, D, H, W, Cin, Cout), EPI_NONE, 0, GemmArgs{x, bp, bias, y, 0}, stream);
+}
+
+// Down conv dgrad: dx fine (+)= scatter(dy[coarse][Cout] * B')
+extern "C" int bcp_down_dgrad(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout,
+                              int accumulate, void* stream) {
+  BCP_REQUIRE(dy && bp && dx, "bcp_down_dgrad: null pointer");
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_down_dgrad: bad shape");
+  return nn_entry("bcp_down_dgrad", k2_problem(K2_DOWN_DGRAD, N, D, H, W, Cin, Cout), EPI_NONE, 0, GemmArgs{dy, bp, nullptr, dx, accumulate}, stream);
+}
+
+// Up (transposed) conv forward: y fine [N][D][H][W][Cout] = scatter(x[coarse][Cin] * B) + bias
+extern "C" int bcp_up_fwd(const float* x, const float* bp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
+                          int Cout, void* stream) {
+  BCP_REQUIRE(x && bp && y, "bcp_up_fwd: null pointer");
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_up_fwd: bad shape");
+  return nn_entry("bcp_up_fwd", k2_problem(K2_UP_FWD, N, D, H, W, Cin, Cout), EPI_NONE, 0, GemmArgs{x, bp, bias, y, 0}, stream);
+}
+
+// Up conv dgrad: dx[coarse][Cin] = gather(dy fine) * B'
+extern "C" int bcp_up_dgrad(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout,
+                            int accumulate, void* stream) {
+  BCP_REQUIRE(dy && bp && dx, "bcp_up_dgrad: null pointer");
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_up_dgrad: bad shape");
+  return nn_entry("bcp_up_dgrad", k2_problem(K2_UP_DGRAD, N, D, H, W, Cin, Cout), EPI_NONE, 0, GemmArgs{dy, bp, nullptr, dx, accumulate}, stream);
+}
+
+extern "C" int bcp_pw_fwd(const float* x, const float* bp, const float* bias, float* y, long long rows, int Cin, int Cout,
+                          void* stream) {
+  BCP_REQUIRE(x && bp && y && rows > 0 && rows < (1LL << 31), "bcp_pw_fwd: bad argument");
+  BCP_REQUIRE(Cin % 16 == 0 && Cout % 16 == 0, "bcp_pw_fwd: channels must be multiples of 16");
+  return nn_entry("bcp_pw_fwd", k2_problem(K2_PW_FWD, (int)rows, 1, 1, 1, Cin, Cout), EPI_NONE, 0, GemmArgs{x, bp, bias, y, 0}, stream);
 }
 
 // The k2s2 / transposed conv forward that also leaves the norm statistics of its output (round 6): stat_partial[groups][rows][Cout][2]
-// doubles, rows = bcp_k2_stat_rows(kind, ...) (kind 0 = down conv, 1 = transposed conv; (D, H, W) the FINE dims as in bcp_down_fwd /
-// bcp_up_fwd); rows == 0: not available for this shape (run the plain entry point and let bcp_norm_fwd make its own pass).
+// doubles, rows = bcp_k2_stat_rows(kind, ...) (kind 0 = down conv, 1 = transposed conv); rows == 0: not available for this shape (run the
+// plain entry point and let bcp_norm_fwd make its own pass).  The entry points themselves do not look at option k2_stats: only the query does.
 extern "C" int bcp_k2_stat_rows(int kind, int N, int D, int H, int W, int Cin, int Cout, int groups) {
-  if (N < 1 || D < 2 || H < 2 || W < 2 || (D | H | W) & 1 || Cin % 16 || Cout % 16 || Cin < 16 || Cout < 16 || groups < 1) return 0;
-  if (options().k2_stats == 0) return 0;
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
+  const K2Problem p = k2_problem(kind == 0 ? K2_DOWN_FWD : K2_UP_FWD, N, D, H, W, Cin, Cout);
   // (k2_stats = 2: only where the output is >= 2^24 elements -- the statistics pass saved there is 19-23 us, the epilogue costs ~11 at every level)
-  if (options().k2_stats == 2 && (long long)(kind == 0 ? M : 8LL * M) * Cout < (1LL << 24)) return 0;
-  StatPlan p;
-  return stat_plan(p, M, kind == 0 ? Cout : 8 * Cout, Cout, groups) ? p.nb : 0;
+  return k2_shape_ok(true, N, D, H, W, Cin, Cout) && groups >= 1 ? gated_route(options().k2_stats, 1LL << 24, p, EPI_FWD_STATS, groups).nb : 0;
 }
 
 extern "C" int bcp_down_fwd_stats(const float* x, const float* bp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
                                   int Cout, double* stat_partial, int groups, void* stream) {
   BCP_REQUIRE(x && bp && y && stat_partial, "bcp_down_fwd_stats: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_down_fwd_stats: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  const int nb = launch_nn_stats(make_map(x, MAP_PATCH, 8 * Cin, Cin, D, H, W), bp, bias, make_map(y, MAP_PLAIN, Cout, 0, 0, 0, 0), M, 8 * Cin,
-                                 Cout, Cout, Cout, 0, stat_partial, groups, nullptr, nullptr, 0, (hipStream_t)stream);
-  BCP_REQUIRE(nb > 0, "bcp_down_fwd_stats: fused statistics unavailable for this shape (check bcp_k2_stat_rows first)");
-  BCP_CHECK_LAUNCH("bcp_down_fwd_stats");
-  return BCP_OK;
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_down_fwd_stats: bad shape");
+  GemmArgs g{x, bp, bias, y, 0};
+  g.partial = stat_partial;
+  return nn_entry("bcp_down_fwd_stats", k2_problem(K2_DOWN_FWD, N, D, H, W, Cin, Cout), EPI_FWD_STATS, groups, g, stream);
 }
 
 extern "C" int bcp_up_fwd_stats(const float* x, const float* bp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
                                 int Cout, double* stat_partial, int groups, void* stream) {
   BCP_REQUIRE(x && bp && y && stat_partial, "bcp_up_fwd_stats: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_up_fwd_stats: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  const int nb = launch_nn_stats(make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), bp, bias, make_map(y, MAP_PATCH, 8 * Cout, Cout, D, H, W), M, Cin,
-                                 8 * Cout, Cout, Cout, 0, stat_partial, groups, nullptr, nullptr, 0, (hipStream_t)stream);
-  BCP_REQUIRE(nb > 0, "bcp_up_fwd_stats: fused statistics unavailable for this shape (check bcp_k2_stat_rows first)");
-  BCP_CHECK_LAUNCH("bcp_up_fwd_stats");
-  return BCP_OK;
-}
-
-// Down conv dgrad: dx fine (+)= scatter(dy[coarse][Cout] * B');  (D,H,W) are the FINE dims
-extern "C" int bcp_down_dgrad(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout,
-                              int accumulate, void* stream) {
-  BCP_REQUIRE(dy && bp && dx, "bcp_down_dgrad: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_down_dgrad: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  launch_nn(make_map(dy, MAP_PLAIN, Cout, 0, 0, 0, 0), bp, nullptr, make_map(dx, MAP_PATCH, 8 * Cin, Cin, D, H, W), M, Cout,
-            8 * Cin, 1, accumulate, (hipStream_t)stream);
-  BCP_CHECK_LAUNCH("bcp_down_dgrad");
-  return BCP_OK;
-}
-
-// Up (transposed) conv forward: y fine [N][D][H][W][Cout] = scatter(x[coarse][Cin] * B) + bias; (D,H,W) FINE dims
-extern "C" int bcp_up_fwd(const float* x, const float* bp, const float* bias, float* y, int N, int D, int H, int W, int Cin,
-                          int Cout, void* stream) {
-  BCP_REQUIRE(x && bp && y, "bcp_up_fwd: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_up_fwd: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  launch_nn(make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), bp, bias, make_map(y, MAP_PATCH, 8 * Cout, Cout, D, H, W), M, Cin, 8 * Cout,
-            Cout, 0, (hipStream_t)stream);
-  BCP_CHECK_LAUNCH("bcp_up_fwd");
-  return BCP_OK;
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_up_fwd_stats: bad shape");
+  GemmArgs g{x, bp, bias, y, 0};
+  g.partial = stat_partial;
+  return nn_entry("bcp_up_fwd_stats", k2_problem(K2_UP_FWD, N, D, H, W, Cin, Cout), EPI_FWD_STATS, groups, g, stream);
 }
 
 // The two dgrads whose epilogue leaves the backward statistics of the norm layer that CONSUMES their output (round 6; as
@@ -1106,37 +1162,28 @@ extern "C" int bcp_up_fwd(const float* x, const float* bp, const float* bias, fl
 // receives (sum dz, sum dz * xhat) for bcp_norm_bwd(partial_in, nb_in = rows), whose statistics pass over (y, da) is then skipped.
 // rows = bcp_k2_bwdstat_rows(kind: 0 down-conv dgrad / 1 transposed-conv dgrad, ...); 0: not available (plain entry points).
 extern "C" int bcp_k2_bwdstat_rows(int kind, int N, int D, int H, int W, int Cin, int Cout, int groups) {
-  if (N < 1 || D < 2 || H < 2 || W < 2 || (D | H | W) & 1 || Cin % 16 || Cout % 16 || Cin < 16 || Cout < 16 || groups < 1) return 0;
-  if (options().k2_bwd_stats == 0 || options().fuse_bwd_stats == 0) return 0;
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
+  const K2Problem p = k2_problem(kind == 0 ? K2_DOWN_DGRAD : K2_UP_DGRAD, N, D, H, W, Cin, Cout);
   // (k2_bwd_stats = 2: only where the output is >= 2^22 elements -- the pass saved there is 23-33 us in the step, the epilogue costs ~11 at every level)
-  if (options().k2_bwd_stats == 2 && (long long)(kind == 0 ? 8LL * M : M) * Cin < (1LL << 22)) return 0;
-  StatPlan p;
-  return stat_plan(p, M, kind == 0 ? 8 * Cin : Cin, Cin, groups) ? p.nb : 0;
+  const int option = options().fuse_bwd_stats == 0 ? 0 : options().k2_bwd_stats;
+  return k2_shape_ok(true, N, D, H, W, Cin, Cout) && groups >= 1 ? gated_route(option, 1LL << 22, p, EPI_BWD_STATS, groups).nb : 0;
 }
 
 extern "C" int bcp_down_dgrad_bwdstats(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout, int accumulate,
                                        const float* y_prev, const float* stats_prev, int act, double* stat_partial, int groups, void* stream) {
   BCP_REQUIRE(dy && bp && dx && y_prev && stats_prev && stat_partial, "bcp_down_dgrad_bwdstats: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_down_dgrad_bwdstats: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  const int nb = launch_nn_stats(make_map(dy, MAP_PLAIN, Cout, 0, 0, 0, 0), bp, nullptr, make_map(dx, MAP_PATCH, 8 * Cin, Cin, D, H, W), M, Cout,
-                                 8 * Cin, Cin, 1, accumulate, stat_partial, groups, y_prev, stats_prev, act, (hipStream_t)stream);
-  BCP_REQUIRE(nb > 0, "bcp_down_dgrad_bwdstats: fused statistics unavailable for this shape (check bcp_k2_bwdstat_rows first)");
-  BCP_CHECK_LAUNCH("bcp_down_dgrad_bwdstats");
-  return BCP_OK;
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_down_dgrad_bwdstats: bad shape");
+  GemmArgs g{dy, bp, nullptr, dx, accumulate};
+  g.partial = stat_partial; g.by = y_prev; g.bstats = stats_prev; g.act = act;
+  return nn_entry("bcp_down_dgrad_bwdstats", k2_problem(K2_DOWN_DGRAD, N, D, H, W, Cin, Cout), EPI_BWD_STATS, groups, g, stream);
 }
 
 extern "C" int bcp_up_dgrad_bwdstats(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout, int accumulate,
                                      const float* y_prev, const float* stats_prev, int act, double* stat_partial, int groups, void* stream) {
   BCP_REQUIRE(dy && bp && dx && y_prev && stats_prev && stat_partial, "bcp_up_dgrad_bwdstats: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_up_dgrad_bwdstats: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  const int nb = launch_nn_stats(make_map(dy, MAP_PATCH, 8 * Cout, Cout, D, H, W), bp, nullptr, make_map(dx, MAP_PLAIN, Cin, 0, 0, 0, 0), M, 8 * Cout,
-                                 Cin, Cin, 1, accumulate, stat_partial, groups, y_prev, stats_prev, act, (hipStream_t)stream);
-  BCP_REQUIRE(nb > 0, "bcp_up_dgrad_bwdstats: fused statistics unavailable for this shape (check bcp_k2_bwdstat_rows first)");
-  BCP_CHECK_LAUNCH("bcp_up_dgrad_bwdstats");
-  return BCP_OK;
+  BCP_REQUIRE(k2_shape_ok(false, N, D, H, W, Cin, Cout), "bcp_up_dgrad_bwdstats: bad shape");
+  GemmArgs g{dy, bp, nullptr, dx, accumulate};
+  g.partial = stat_partial; g.by = y_prev; g.bstats = stats_prev; g.act = act;
+  return nn_entry("bcp_up_dgrad_bwdstats", k2_problem(K2_UP_DGRAD, N, D, H, W, Cin, Cout), EPI_BWD_STATS, groups, g, stream);
 }
 
 // Round 6: the transposed conv + its norm layer with the conv output RECOMPUTED instead of stored (networks/VNet.py:101-113 UpsamplingDeconvBlock:
@@ -1146,20 +1193,15 @@ extern "C" int bcp_up_dgrad_bwdstats(const float* dy, const float* bp, float* dx
 // that is 224 MB less per forward and 192 MB less per backward pass (y written once and read two / two times before).  Same arithmetic per
 // element as bcp_up_fwd + bcp_norm_fwd / bcp_norm_bwd (k_norm_apply / k_col_partial<1> / k_norm_bwd_apply); the statistics are summed as in
 // bcp_up_fwd_stats (fp32 lane partials, fp64 behind them).  rows = bcp_up_norm_rows(...): 0 = shape not served (or option up_recompute off).
-namespace bcp {      // csrc/norm.hip
-void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
-                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null);
-void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
-                              float* c1c2raw, hipStream_t s, float* amax_clear_or_null);
+static GemmRoute up_norm_route(K2Problem& p, int N, int D, int H, int W, int Cin, int Cout, int groups) {      // the statistics pass; the apply pass walks the same tiles
+  p = k2_problem(K2_UP_FWD, N, D, H, W, Cin, Cout);
+  if (!k2_shape_ok(true, N, D, H, W, Cin, Cout) || groups < 1 || N % groups) return GemmRoute{};
+  return gated_route(options().up_recompute, 1LL << 24, p, EPI_RC_FWD_STATS, groups);      // (2: the top level only)
 }
 
 extern "C" int bcp_up_norm_rows(int N, int D, int H, int W, int Cin, int Cout, int groups) {
-  if (N < 1 || D < 2 || H < 2 || W < 2 || (D | H | W) & 1 || Cin % 16 || Cout % 16 || Cin < 16 || Cout < 16 || groups < 1 || N % groups) return 0;
-  if (options().up_recompute == 0) return 0;
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  if (options().up_recompute == 2 && 8LL * M * Cout < (1LL << 24)) return 0;      // (2: the top level only)
-  StatPlan p;
-  return stat_plan(p, M, 8 * Cout, Cout, groups) ? p.nb : 0;
+  K2Problem p;
+  return up_norm_route(p, N, D, H, W, Cin, Cout, groups).nb;
 }
 
 extern "C" size_t bcp_up_norm_workspace_bytes(int N, int D, int H, int W, int Cin, int Cout, int groups) {
@@ -1172,17 +1214,19 @@ extern "C" int bcp_up_fwd_norm(const float* x, const float* bp, const float* bia
                                const float* residual, float* stats, void* workspace, float* out, float* amax_out_or_null, void* stream) {
   BCP_REQUIRE(x && bp && stats && workspace && out && groups >= 1, "bcp_up_fwd_norm: null pointer / bad groups");
   BCP_REQUIRE(aligned16(out) && aligned16(stats) && (!residual || aligned16(residual)), "bcp_up_fwd_norm: alignment");
-  const int rows0 = bcp_up_norm_rows(N, D, H, W, Cin, Cout, groups);
-  BCP_REQUIRE(rows0 > 0, "bcp_up_fwd_norm: shape not served (check bcp_up_norm_rows first)");
+  K2Problem p;
+  GemmRoute r = up_norm_route(p, N, D, H, W, Cin, Cout, groups);
+  BCP_REQUIRE(r.served, "bcp_up_fwd_norm: shape not served (check bcp_up_norm_rows first)");
   hipStream_t s = (hipStream_t)stream;
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
   double* partial = reinterpret_cast<double*>(workspace);
-  const RowMap A = make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), Cm = make_map(out, MAP_PATCH, 8 * Cout, Cout, D, H, W);
-  const int rows = launch_nn_mode<3>(A, bp, bias, Cm, M, Cin, 8 * Cout, Cout, Cout, 0, partial, groups, nullptr, nullptr, 0, nullptr, nullptr, nullptr, s);
-  BCP_REQUIRE(rows == rows0, "bcp_up_fwd_norm: internal row count mismatch");
-  norm_fwd_finalize_launch(partial, rows, groups, Cout, (long long)N / groups * D * H * W, gamma, beta, running_mean, running_var, momentum, eps, stats, s,
+  GemmArgs g{x, bp, bias, out, 0};
+  g.partial = partial;
+  nn_launch(r, p, g, s);
+  norm_fwd_finalize_launch(partial, r.nb, groups, Cout, (long long)N / groups * D * H * W, gamma, beta, running_mean, running_var, momentum, eps, stats, s,
                            amax_out_or_null);
-  launch_nn_mode<4>(A, bp, bias, Cm, M, Cin, 8 * Cout, Cout, Cout, 0, nullptr, groups, nullptr, stats, act, residual, nullptr, amax_out_or_null, s);
+  r.mode = EPI_RC_FWD_APPLY;
+  g.partial = nullptr; g.bstats = stats; g.act = act; g.aux = residual; g.amax = amax_out_or_null;
+  nn_launch(r, p, g, s);
   BCP_CHECK_LAUNCH("bcp_up_fwd_norm");
   return BCP_OK;
 }
@@ -1193,49 +1237,25 @@ extern "C" int bcp_up_norm_bwd(const float* x, const float* bp, const float* bia
   BCP_REQUIRE(x && bp && da && stats && workspace && dy && groups >= 1, "bcp_up_norm_bwd: null pointer / bad groups");
   BCP_REQUIRE(aligned16(da) && aligned16(dy), "bcp_up_norm_bwd: alignment");
   BCP_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "bcp_up_norm_bwd: dgamma and dbeta come together");
-  const int rows0 = bcp_up_norm_rows(N, D, H, W, Cin, Cout, groups);
-  BCP_REQUIRE(rows0 > 0, "bcp_up_norm_bwd: shape not served (check bcp_up_norm_rows first)");
+  K2Problem p;
+  GemmRoute r = up_norm_route(p, N, D, H, W, Cin, Cout, groups);
+  BCP_REQUIRE(r.served, "bcp_up_norm_bwd: shape not served (check bcp_up_norm_rows first)");
   hipStream_t s = (hipStream_t)stream;
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
   double* partial = reinterpret_cast<double*>(workspace);
-  float* c1c2raw = reinterpret_cast<float*>(partial + (size_t)groups * rows0 * Cout * 2);
-  const RowMap A = make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), Cm = make_map(dy, MAP_PATCH, 8 * Cout, Cout, D, H, W);
-  const int rows = launch_nn_mode<5>(A, bp, bias, Cm, M, Cin, 8 * Cout, Cout, Cout, 0, partial, groups, nullptr, stats, act, da, nullptr, nullptr, s);
-  BCP_REQUIRE(rows == rows0, "bcp_up_norm_bwd: internal row count mismatch");
-  norm_bwd_finalize_launch(partial, rows, groups, Cout, (long long)N / groups * D * H * W, dgamma, dbeta, accumulate, c1c2raw, s, nullptr);
-  launch_nn_mode<6>(A, bp, bias, Cm, M, Cin, 8 * Cout, Cout, Cout, 0, nullptr, groups, nullptr, stats, act, da, c1c2raw, nullptr, s);
+  float* c1c2raw = reinterpret_cast<float*>(partial + (size_t)groups * r.nb * Cout * 2);
+  GemmArgs g{x, bp, bias, dy, 0};
+  g.partial = partial; g.bstats = stats; g.act = act; g.aux = da;
+  r.mode = EPI_RC_BWD_STATS;
+  nn_launch(r, p, g, s);
+  norm_bwd_finalize_launch(partial, r.nb, groups, Cout, (long long)N / groups * D * H * W, dgamma, dbeta, accumulate, c1c2raw, s, nullptr);
+  r.mode = EPI_RC_BWD_APPLY;
+  g.partial = nullptr; g.c1c2 = c1c2raw;
+  nn_launch(r, p, g, s);
   BCP_CHECK_LAUNCH("bcp_up_norm_bwd");
   return BCP_OK;
 }
 
-// Up conv dgrad: dx[coarse][Cin] = gather(dy fine) * B'
-extern "C" int bcp_up_dgrad(const float* dy, const float* bp, float* dx, int N, int D, int H, int W, int Cin, int Cout,
-                            int accumulate, void* stream) {
-  BCP_REQUIRE(dy && bp && dx, "bcp_up_dgrad: null pointer");
-  BCP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0 && Cin % 16 == 0 && Cout % 16 == 0, "bcp_up_dgrad: bad shape");
-  const int M = N * (D / 2) * (H / 2) * (W / 2);
-  launch_nn(make_map(dy, MAP_PATCH, 8 * Cout, Cout, D, H, W), bp, nullptr, make_map(dx, MAP_PLAIN, Cin, 0, 0, 0, 0), M, 8 * Cout,
-            Cin, 1, accumulate, (hipStream_t)stream);
-  BCP_CHECK_LAUNCH("bcp_up_dgrad");
-  return BCP_OK;
-}
-
-extern "C" int bcp_pw_fwd(const float* x, const float* bp, const float* bias, float* y, long long rows, int Cin, int Cout,
-                          void* stream) {
-  BCP_REQUIRE(x && bp && y && rows > 0 && rows < (1LL << 31), "bcp_pw_fwd: bad argument");
-  BCP_REQUIRE(Cin % 16 == 0 && Cout % 16 == 0, "bcp_pw_fwd: channels must be multiples of 16");
-  launch_nn(make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), bp, bias, make_map(y, MAP_PLAIN, Cout, 0, 0, 0, 0), (int)rows, Cin, Cout, Cout,
-            0, (hipStream_t)stream);
-  BCP_CHECK_LAUNCH("bcp_pw_fwd");
-  return BCP_OK;
-}
-
-extern "C" size_t bcp_tn_workspace_bytes(long long M, int K, int N) {
-  const int nt = tn_nt(N);
-  const int g0 = tn_groups((int)M, K, N, nt);
-  const int rpg = cdiv(cdiv(M, g0), 64) * 64;
-  return (size_t)cdiv(M, rpg) * K * N * sizeof(float);
-}
+extern "C" size_t bcp_tn_workspace_bytes(long long M, int K, int N) { return (size_t)tn_route(M, K, N).G * K * N * sizeof(float); }
 
 // Weight gradients.  kind selects the layer type; (D,H,W) are the FINE dims for the k2 kinds.
 //   BCP_WG_DOWN: x fine [.,Cin], dy coarse [.,Cout] -> dw[Cout][Cin][8]
@@ -1247,27 +1267,10 @@ extern "C" int bcp_k2_wgrad(const float* x, const float* dy, float* dw, int N, i
 
   BCP_REQUIRE(x && dy && dw && workspace, "bcp_k2_wgrad: null pointer");
   BCP_REQUIRE(Cin % 16 == 0 && Cout % 16 == 0, "bcp_k2_wgrad: channels must be multiples of 16");
-  float* ws = reinterpret_cast<float*>(workspace);
-  hipStream_t s = (hipStream_t)stream;
-  if (kind == BCP_WG_DOWN) {
-    const int M = N * (D / 2) * (H / 2) * (W / 2);
-    Idx4 ix = {Cin, Cout, 1, 8, 0, (long long)Cin * 8};  // k = s*Cin + ci, n = co -> dw[co][ci][s]
-    launch_tn(make_map(x, MAP_PATCH, 8 * Cin, Cin, D, H, W), make_map(dy, MAP_PLAIN, Cout, 0, 0, 0, 0), ws, dw, M, 8 * Cin, Cout, ix,
-              accumulate, s);
-  } else if (kind == BCP_WG_UP) {
-    const int M = N * (D / 2) * (H / 2) * (W / 2);
-    Idx4 ix = {Cin, Cout, 0, (long long)Cout * 8, 1, 8};  // k = ci, n = s*Cout + co -> dw[ci][co][s]
-    launch_tn(make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), make_map(dy, MAP_PATCH, 8 * Cout, Cout, D, H, W), ws, dw, M, Cin, 8 * Cout, ix,
-              accumulate, s);
-  } else if (kind == BCP_WG_PW) {
-    const long long M = (long long)N * D * H * W;
-    BCP_REQUIRE(M < (1LL << 31), "bcp_k2_wgrad: too many rows");
-    Idx4 ix = {Cin, Cout, 0, 1, 0, (long long)Cin};  // k = ci, n = co -> dw[co][ci]
-    launch_tn(make_map(x, MAP_PLAIN, Cin, 0, 0, 0, 0), make_map(dy, MAP_PLAIN, Cout, 0, 0, 0, 0), ws, dw, (int)M, Cin, Cout, ix,
-              accumulate, s);
-  } else {
-    BCP_REQUIRE(false, "bcp_k2_wgrad: unknown kind %d", kind);
-  }
+  BCP_REQUIRE(kind == BCP_WG_DOWN || kind == BCP_WG_UP || kind == BCP_WG_PW, "bcp_k2_wgrad: unknown kind %d", kind);
+  const K2Problem p = k2_problem(kind == BCP_WG_DOWN ? K2_DOWN_FWD : kind == BCP_WG_UP ? K2_UP_FWD : K2_PW_FWD, N, D, H, W, Cin, Cout);
+  BCP_REQUIRE(p.M < (1LL << 31), "bcp_k2_wgrad: too many rows");
+  tn_launch(p, x, dy, reinterpret_cast<float*>(workspace), dw, accumulate, (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_k2_wgrad");
   return BCP_OK;
 }
@@ -1351,10 +1354,6 @@ extern "C" int bcp_pw16_bwd_norm(const float* x_raw, const float* stats, const f
 }
 
 // ---- the head's backward through the norm (kernels above).  workspace: bcp_pw16_bwd_norm_bwd_workspace_bytes
-namespace bcp {      // csrc/norm.hip
-void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
-                              float* c1c2raw, hipStream_t s, float* amax_clear_or_null);
-}
 static int pw16_nbps(long long vps, int N) {
   long long nb = vps / 1024;                       // >= 16 float4 per thread: the block reduction (18-28 fp64 values) is the kernel's tail
   const long long cap = 768 / N < 1 ? 1 : 768 / N;  // k_pw16_bwd_stats holds 130 VGPRs (128 by force spills): three workgroups per CU are resident, one round of them

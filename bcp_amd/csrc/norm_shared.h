@@ -39,6 +39,13 @@ __device__ __forceinline__ bool reduce_partials(const double* __restrict__ parti
   return true;
 }
 
+// ---- the finalize kernels of csrc/norm.hip behind a statistics pass that somebody else made (csrc/gemm.hip bcp_up_fwd_norm / bcp_up_norm_bwd):
+// partial[G][nb][C][2] -> the statistics table float[5][G][C] (and the running statistics) / dgamma, dbeta and c1c2raw = float[4][G][C]
+void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null);
+void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
+                              float* c1c2raw, hipStream_t s, float* amax_clear_or_null);
+
 // ---- per-sample streams of csrc/norm.hip launched for a GroupNorm layer (groups of the streams = samples; table = float[5][N][C])
 // partial rows per sample the statistics passes below leave (the workspace holds N x this many rows of [C][2] doubles)
 int per_sample_stat_rows(long long rows_per_sample, int C);

@@ -352,15 +352,18 @@ static std::string symbol_of(const void* fn) {
   return name;
 }
 
-bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem) {
+bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem, const std::string* values) {
   const int mode = g_log_mode.load();
   if (mode == 0) return true;
   char tail[128];
   snprintf(tail, sizeof tail, "|%u,%u,%u|%u,%u,%u|%zu\n", gx, gy, gz, bx, by, bz, shmem);
   std::lock_guard<std::mutex> lk(g_log_mu);
   g_log += "L|" + symbol_of(fn) + tail;
-  return mode != 2;
+  if (values) g_log += "P|" + values->substr(0, values->empty() ? 0 : values->size() - 1) + "\n";      // (without the last comma)
+  return mode != 2 && mode != 3;
 }
+
+bool log_args() { return g_log_mode.load() == 3; }
 
 void note_attr(const void* fn, int value) {
   if (g_log_mode.load() == 0) return;

@@ -19,7 +19,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 #include <sys/mman.h>
@@ -59,9 +61,17 @@ inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
 enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 // launch log (tests/test_emu_conv3_routes.py): mode 0 = off, 1 = note every launch and attribute call, 2 = note them and do not execute
-// the launches (entry points may then be handed any non-null aligned buffer).  Read through bcpemu_log_take (emu_runtime.cpp).
+// the launches (entry points may then be handed any non-null aligned buffer), 3 = as 2 plus one "P|v,v,.." record behind each launch
+// record with the kernel's arguments of arithmetic type in order (tests/test_emu_gemm_routes.py; struct and pointer arguments are not
+// recorded).  Read through bcpemu_log_take (emu_runtime.cpp).
 namespace bcpemu {
-bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem);   // false: do not execute
+// false: do not execute.  values (mode 3): the "P|" record's text, written with the "L|" record under one hold of the log's lock
+bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem, const std::string* values = nullptr);
+bool log_args();                              // mode 3
+template <class T> inline void fmt_arg(std::string& s, const T& v) {
+  if constexpr (std::is_integral<T>::value) s += std::to_string((long long)v) + ",";
+  else if constexpr (std::is_floating_point<T>::value) { char b[40]; snprintf(b, sizeof b, "%.9g,", (double)v); s += b; }
+}
 void note_attr(const void* fn, int value);
 }
 template <class F> inline hipError_t hipFuncSetAttribute(F f, hipFuncAttribute, int v) { ::bcpemu::note_attr((const void*)f, v); return hipSuccess; }
@@ -313,7 +323,10 @@ using std::min;
 // ---- launch
 template <class K, class... Args>
 inline void bcpemu_launch(K kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
-  if (!::bcpemu::note_launch((const void*)kernel, grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem)) return;
+  std::string values;
+  const bool with_args = ::bcpemu::log_args();
+  if (with_args) (::bcpemu::fmt_arg(values, args), ...);
+  if (!::bcpemu::note_launch((const void*)kernel, grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem, with_args ? &values : nullptr)) return;
   std::function<void()> body = [=]() { kernel(args...); };
   ::bcpemu::run_grid(grid, block, shmem, body);
 }

@@ -192,14 +192,14 @@ def lds_attribute_violations(logs):
     return sorted(set(bad))
 
 
-def exported_kernels(path=EMU):
+def exported_kernels(path=EMU, families=KERNEL_FAMILIES):
     out = subprocess.run(["nm", "-D", "-C", "--defined-only", path], check=True, capture_output=True, text=True).stdout
     syms = set()
     for ln in out.splitlines():
         name = ln.split(" ", 2)[2]
         name = name[5:] if name.startswith("void ") else name
         name = name.split("(")[0]
-        if name.startswith("bcp::") and name[5:].startswith(KERNEL_FAMILIES):
+        if name.startswith("bcp::") and name[5:].startswith(families):
             syms.add(name)
     return syms
 
