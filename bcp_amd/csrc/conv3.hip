@@ -19,6 +19,7 @@
 // (32 cycles / instruction / SIMD) that LDS bandwidth is not the limiter; the structure is chosen
 // so every wave issues MT*NT*4 back-to-back MFMAs per tap per (MT+NT) ds_read_b128.
 #include "conv3_defs.h"
+#include "norm_shared.h"
 #include "../../include/bcp_hip.h"
 #include <cstdlib>
 #include <cstdio>
@@ -1918,13 +1919,7 @@ extern "C" int bcp_conv3_c1_fwd_stats(const float* x, const float* w, const floa
 // statistics from the accumulators, pass 2 runs the same MFMAs again and stores the activation; the backward recomputes y the same way
 // next to da.  128 MB of y written + read back twice per direction at the LA size become two 8 MB reads of x.
 // workspace: bcp_conv3_c1_norm_workspace_bytes.  Results are bit-identical to bcp_conv3_c1_fwd_stats + bcp_norm_fwd / bcp_norm_bwd.
-namespace bcp {      // csrc/norm.hip
-void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
-                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null);
-void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
-                              float* c1c2raw, hipStream_t s, float* amax_clear_or_null);
-}
-
+// (the finalize launches between the two passes: csrc/norm.hip, declared in csrc/norm_shared.h)
 extern "C" size_t bcp_conv3_c1_norm_workspace_bytes(int N, int D, int H, int W, int KD, int groups) {
   const int rows = bcp_conv3_c1_stat_rows(N, D, H, W, KD, groups);
   return rows > 0 ? (size_t)groups * rows * 16 * 2 * sizeof(double) + (size_t)4 * groups * 16 * sizeof(float) : 0;

@@ -18,16 +18,7 @@
 
 namespace bcp {
 
-struct NormEpilogue {
-  const float* chan_scale;     // nullable [N][C]: Dropout3d keep*1/(1-p) per (sample, channel)
-  const uint8_t* elem_mask;    // nullable [rows][C]: elementwise Dropout keep mask
-  float elem_scale;            // 1/(1-p) for elem_mask
-  long long rows_per_sample;   // spatial size (rows per n) for chan_scale indexing
-  int act;
-  const unsigned long long* mask_seed;   // nullable (round 4): device seed of an elementwise Dropout whose keep bits are EVALUATED here
-  float p_keep;                          //   (bern_keep, common.h: the bits bcp_bernoulli_dev would write) instead of read from elem_mask
-};
-// the four mask bytes of elements e .. e+3: loaded, or evaluated from the seed
+// (NormEpilogue: csrc/norm_shared.h)  the four mask bytes of elements e .. e+3: loaded, or evaluated from the seed
 #define BCP_NORM_MASK_PROLOGUE(ep)                                                                                  \
   unsigned mseed_lo = 0, mseed_hi = 0;                                                                              \
   if ((ep).mask_seed) { const unsigned long long s_ = *(ep).mask_seed; mseed_lo = (unsigned)s_; mseed_hi = (unsigned)(s_ >> 32); } \
@@ -1019,6 +1010,8 @@ __global__ __launch_bounds__(kOwnThreads) void k_norm_own_bwd(OwnCommon a, OwnBw
   }
 }
 
+// ---- host dispatch: one problem record (norm_problem), one route (norm_route: decide; both records: csrc/norm_shared.h), one launcher per
+// direction (norm_fwd_launch / norm_bwd_launch: execute).  tests/test_emu_norm_routes.py pins every launch of every entry point of the family.  The rules of the route:
 // -> GS (groups per workgroup) when the one-launch form serves the shape, else 0; cw = channels per workgroup: the narrowest of 8 / 16 / 32 that
 // keeps the launch at <= 32 workgroups (a workgroup moves its bytes at one CU's rate: eight 32-channel workgroups were slower than the
 // two-launch chain at LA's 7x7x5 x 256 level).  ordered: running statistics / parameter gradients tie the groups together
@@ -1032,53 +1025,37 @@ static inline int own_gs(int G, long long R, int C, bool ordered, int& cw) {
   if (R > 512 || R > (long long)kOwnMaxP * ((kOwnThreads / (cw / 4)) / GS)) return 0;      // (a few hundred rows: beyond that the narrow chunks are bound by one cache line per lane -- pancreas 12^3 x 128 through here: -2.3 % on the step)
   return GS;
 }
-#define BCP_OWN_LAUNCH(KERN, R_, GS_, G_, C_, s_, a_, b_)                                                              \
-  do {                                                                                                                \
-    const int rpp_ = (kOwnThreads / ((a_).cw / 4)) / (GS_);                                                             \
-    const int P_ = (int)(((R_) + rpp_ - 1) / rpp_);                                                                   \
-    const dim3 grid_((C_) / (a_).cw, (G_) / (GS_));                                                                        \
-    if (P_ <= 1) hipLaunchKernelGGL((KERN<1>), grid_, dim3(kOwnThreads), 0, s_, a_, b_);                              \
-    else if (P_ == 2) hipLaunchKernelGGL((KERN<2>), grid_, dim3(kOwnThreads), 0, s_, a_, b_);                         \
-    else hipLaunchKernelGGL((KERN<4>), grid_, dim3(kOwnThreads), 0, s_, a_, b_);                                      \
-  } while (0)
-
 // the fused apply passes serve: option norm_fuse_fin on, few partial rows, 16 <= C <= 256 (C a power of two: whole chunks)
 static inline bool fin_fused_ok(int nb, int C) { return options().norm_fuse_fin != 0 && nb >= 1 && nb <= kFinMaxRows && C >= 16 && C <= 256; }
-static inline dim3 fin_grid(long long seg_rows, int nseg, int C, bool runner) {
+static inline dim3 fused_grid(long long seg_rows, int nseg, int C, bool runner) {
   const int cw = C < kFinChunk ? C : kFinChunk, slots = 256 / (cw / 4);
   long long gx = (seg_rows + (long long)slots * 4 - 1) / ((long long)slots * 4);      // four rows per thread and trip
   const long long cap = 1024 / ((long long)nseg * (C / cw)) < 1 ? 1 : 1024 / ((long long)nseg * (C / cw));
   if (gx > cap) gx = cap;
   return dim3((unsigned)(gx < 1 ? 1 : gx) + (runner ? 1u : 0u), (unsigned)nseg, (unsigned)(C / cw));
 }
-
-static inline bool skip_fin(long long rpg) { const int w = options().whatif; return (w & 1) || ((w & 2) && rpg <= 4096); }
-static inline bool skip_app(long long rpg) { return ((options().whatif & 2) && rpg <= 4096) || ((options().whatif & 16) && rpg >= 100000); }
-static inline bool skip_bstat(long long rpg) { return (options().whatif & 32) && rpg >= 100000; }
+// partial rows per group of a statistics pass over the tensor: enough blocks to fill the chip, but at least ~64 rows per thread-slot (LDS reduce)
 static inline int norm_blocks(long long rows_per_group, int C) {
-  // enough blocks to fill the chip, but at least ~64 rows per thread-slot to amortise the LDS reduce
-  const int slots = 256 / (C / 4);
+  const int slots = C <= 1024 ? 256 / (C / 4) : 1;      // (wider: a finalize step behind somebody else's pass -- no pass of this file serves it)
   long long nb = rows_per_group / ((long long)slots * 16);
   if (nb > 1024) nb = 1024;
   if (nb < 1) nb = 1;
   return (int)nb;
 }
-
-// statistics pass that also sums split-K slabs (k_col_partial<MODE, true>): it moves nslab + 1 times the tensor and serves the deep levels
-// only (<= 4096 rows per group), where norm_blocks' ~64 rows per thread-slot would leave 3-15 workgroups to do it (round 4, measured:
-// LA step 6.10 vs 6.02 ms with the slab-sum launch) -- one row per thread-slot and pass, at most ~256 workgroups per launch
-static inline int norm_blocks_slabs(long long rows_per_group, int C, int G, bool sizing = false /* workspace size: whatever the options say later */) {
+// ... of one that also sums split-K slabs (k_col_partial<MODE, true>): it moves nslab + 1 times the tensor and serves the deep levels
+// only (<= kSlabMaxRows rows per group), where norm_blocks' ~64 rows per thread-slot would leave 3-15 workgroups to do it (round 4, measured:
+// LA step 6.10 vs 6.02 ms with the slab-sum launch) -- one row per thread-slot and pass, at most ~256 workgroups per launch.  This is the
+// most rows any option leaves (norm_route lowers it in front of a fused apply pass): what the workspace is sized for
+constexpr long long kSlabMaxRows = 4096;
+static inline int slab_rows_max(long long rows_per_group, int C, int G) {
   const int slots = 256 / (C / 4);
   long long nb = (rows_per_group + slots - 1) / slots;
-  long long cap = G >= 256 ? 1 : 256 / G;
-  // (round 6) the fused apply pass behind this launch re-reads the partial rows in EVERY workgroup (k_norm_apply_fin): fewer, longer blocks
-  if (!sizing && options().norm_fuse_fin != 0 && C <= 256 && cap > options().norm_fin_rows && options().norm_fin_rows > 0) cap = options().norm_fin_rows;
+  const long long cap = G >= 256 ? 1 : 256 / G;
   if (nb > cap) nb = cap;
   const int plain = norm_blocks(rows_per_group, C);
   return (int)(nb < plain ? plain : nb);
 }
-
-static inline int apply_grid(long long nvec, int nseg) {
+static inline int apply_blocks(long long nvec, int nseg) {
   const int vec = options().norm_apply_vec > 0 ? options().norm_apply_vec : 4, capw = options().norm_apply_cap > 0 ? options().norm_apply_cap : 2048;
   long long g = (nvec + 256 * vec - 1) / (256 * vec);      // 4 float4 per thread per trip
   const long long cap = capw / nseg < 1 ? 1 : capw / nseg;
@@ -1086,27 +1063,107 @@ static inline int apply_grid(long long nvec, int nseg) {
   return (int)(g < 1 ? 1 : g);
 }
 
-// segments (see k_col_partial): the finer of (group, sample) when a per-sample channel scale is present
-struct Segs { long long seg_rows; int spg; int nbps; };
-static inline Segs make_segs(int G, long long rows_per_group, int C, const NormEpilogue& ep, int nblocks = 0) {
-  Segs sg{rows_per_group, 1, nblocks > 0 ? nblocks : norm_blocks(rows_per_group, C)};
-  if (ep.chan_scale && ep.rows_per_sample < rows_per_group) {
-    sg.seg_rows = ep.rows_per_sample;
-    sg.spg = (int)(rows_per_group / ep.rows_per_sample);
-    sg.nbps = sg.nbps / sg.spg < 1 ? 1 : sg.nbps / sg.spg;
+// Pure: its arguments and options().  A new form of the norm is one more NormForm value, its rule here and its launch in the launchers.
+NormRoute norm_route(NormDir dir, NormSrc src, const NormProblem& p, bool has_out, bool ordered) {
+  NormRoute r{};
+  const long long R = p.rows_per_group;
+  const int w = options().whatif;
+  r.skip_fin = (w & 1) || ((w & 2) && R <= 4096);
+  r.skip_app = ((w & 2) && R <= 4096) || ((w & 16) && R >= 100000);
+  r.skip_bstat = (w & 32) && R >= 100000;
+  int rows = norm_blocks(R, p.C);
+  if (src == NormSrc::Slabs) {
+    rows = slab_rows_max(R, p.C, p.G);
+    // (round 6) the fused apply pass behind this launch re-reads the partial rows in EVERY workgroup (k_norm_apply_fin): fewer, longer blocks
+    const int few = options().norm_fin_rows;
+    if (options().norm_fuse_fin != 0 && p.C <= 256 && few > 0 && rows > few) rows = few > norm_blocks(R, p.C) ? few : norm_blocks(R, p.C);
   }
-  return sg;
+  // Workspace: [G][cap_rows][C][2] doubles, then c1c2raw.  A route writes nb = max(1, rows / spg) * spg <= max(rows, spg) <= rows +
+  // kMaxSamplesPerGroup = cap_rows partial rows per group, and rows <= the query's: norm_blocks <= slab_rows_max where the slab pass
+  // serves (the query takes that one there), and no option raises either.  So every route's rows and its c1c2raw fit what bcp_norm_workspace_bytes answered, whichever
+  // options were set then.
+  r.cap_rows = rows + kMaxSamplesPerGroup;
+  r.c1_offset = (size_t)p.G * r.cap_rows * p.C * 2 * sizeof(double);
+  r.nbps = rows / p.spg < 1 ? 1 : rows / p.spg, r.nseg = p.G * p.spg, r.nb = r.nbps * p.spg;
+  r.stat_grid = dim3(r.nbps, r.nseg);
+  r.fin_grid = dim3(p.G * (p.C / 16));
+  r.apply_grid = dim3(apply_blocks(p.seg_rows * (p.C / 4), r.nseg), r.nseg);
+  r.fused_grid = fused_grid(p.seg_rows, r.nseg, p.C, ordered);
+  const bool streams = src != NormSrc::Partial && has_out;      // this call reads the tensor twice: the forms that save a launch apply
+  if (streams && (r.GS = own_gs(p.G, R, p.C, ordered, r.cw)) != 0) {      // (round 6) the smallest levels: ONE launch
+    const int rpp = (kOwnThreads / (r.cw / 4)) / r.GS, passes = (int)((R + rpp - 1) / rpp);
+    r.form = NormForm::Own, r.P = passes <= 1 ? 1 : passes == 2 ? 2 : 4, r.own_grid = dim3(p.C / r.cw, p.G / r.GS);
+    return r;
+  }
+  r.form = streams && fin_fused_ok(r.nb, p.C) ? NormForm::Fused : NormForm::Chain;      // (round 6) Fused: the apply pass finalises the statistics itself
+  r.stats = src != NormSrc::Partial && !(dir == NormDir::Bwd && r.skip_bstat);
+  r.finalize = r.form == NormForm::Chain && !r.skip_fin;
+  if (r.form == NormForm::Chain) r.tail = has_out ? (r.skip_app ? NormTail::None : NormTail::Apply) : ordered ? NormTail::Params : NormTail::None;
+  return r;
 }
-static constexpr int kMaxSamplesPerGroup = 64;
 
-// ---- finalize steps for producers that keep the statistics pass AND the apply pass in their own kernels (the fused first layer,
-// csrc/conv3.hip bcp_conv3_c1_norm_fwd / _bwd): same kernels as bcp_norm_fwd / bcp_norm_bwd run between their two passes
-void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
-                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null) {
-  float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C, *var_unb = stats + 4LL * G * C;
-  if (!skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, gamma, beta, running_mean,
-                     running_var, momentum, eps, mean, rstd, scale, shift, var_unb, amax_clear_or_null);
-  if (running_mean) hipLaunchKernelGGL(k_norm_running_only, dim3(1), dim3(256), 0, s, mean, var_unb, G, C, running_mean, running_var, momentum);
+int norm_problem(const char* fn, int G, long long rows_per_group, int C, const NormEpilogue& ep, NormProblem& p) {
+  BCP_REQUIRE(G >= 1 && rows_per_group >= 1, "%s: bad extents", fn);
+  BCP_REQUIRE(C >= 16 && C <= 1024 && (C & (C - 1)) == 0, "%s: C=%d unsupported (need a power of two in 16..1024)", fn, C);
+  p = NormProblem{G, rows_per_group, C, ep, rows_per_group, 1};
+  if (ep.rows_per_sample <= 0) p.ep.rows_per_sample = rows_per_group;
+  if (!ep.chan_scale) return BCP_OK;
+  BCP_REQUIRE(rows_per_group % p.ep.rows_per_sample == 0 && rows_per_group / p.ep.rows_per_sample <= kMaxSamplesPerGroup,
+              "%s: a group must hold 1..%d whole samples", fn, kMaxSamplesPerGroup);
+  p.seg_rows = p.ep.rows_per_sample;
+  p.spg = (int)(rows_per_group / p.seg_rows);
+  return BCP_OK;
+}
+
+// ---- the launch sites: each __global__ of the family is named once, here or in a table
+static const decltype(&k_col_partial<0, false>) kColPartial[2][2] = {{k_col_partial<0, false>, k_col_partial<0, true>}, {k_col_partial<1, false>, k_col_partial<1, true>}};      // [MODE][SL]
+static void (*const kOwnFwd[3])(OwnCommon, OwnFwd) = {k_norm_own_fwd<1>, k_norm_own_fwd<2>, k_norm_own_fwd<4>};      // [P >> 1]
+static void (*const kOwnBwd[3])(OwnCommon, OwnBwd) = {k_norm_own_bwd<1>, k_norm_own_bwd<2>, k_norm_own_bwd<4>};
+
+// mode 0: (sum y, sum y^2), t unused; mode 1: (sum dz, sum dz * xhat) with xhat and the activation pattern from the table t
+static void col_partial_launch(int mode, const NormRoute& r, const NormProblem& p, const float* y, const float* da, const NormTable& t, double* partial,
+                               const SlabSrc& sl, float* amax_clear_or_null, hipStream_t s) {
+  hipLaunchKernelGGL(kColPartial[mode][sl.slabs != nullptr], r.stat_grid, dim3(256), 0, s, y, da, t.scale, t.shift, t.mean, t.rstd, p.ep, p.seg_rows, p.spg, p.C,
+                     partial, sl, amax_clear_or_null);
+}
+static void fwd_finalize_launch(const NormRoute& r, const NormProblem& p, const FinFwd& f, float* amax_clear_or_null, hipStream_t s) {
+  const NormTable t = norm_table(f.stats, p.G, p.C);
+  hipLaunchKernelGGL(k_norm_finalize, r.fin_grid, dim3(kFinalizeThreads), 0, s, f.partial, f.nb, p.G, p.C, p.rows_per_group, f.gamma, f.beta, f.running_mean,
+                     f.running_var, f.momentum, f.eps, t.mean, t.rstd, t.scale, t.shift, t.var_unb, amax_clear_or_null);
+}
+// statistics only: the consumer applies the normalisation itself (bcp_pw16_fwd_norm); otherwise the apply pass carries the running-statistics update
+static void running_only_launch(const NormProblem& p, const FinFwd& f, hipStream_t s) {
+  const NormTable t = norm_table(f.stats, p.G, p.C);
+  hipLaunchKernelGGL(k_norm_running_only, dim3(1), dim3(256), 0, s, t.mean, t.var_unb, p.G, p.C, f.running_mean, f.running_var, f.momentum);
+}
+static void fwd_apply_launch(const NormRoute& r, const NormProblem& p, const float* x, const FinFwd& f, const float* residual, float* out, long long out_ld,
+                             float* amax_out, hipStream_t s) {
+  const NormTable t = norm_table(f.stats, p.G, p.C);
+  hipLaunchKernelGGL(k_norm_apply, r.apply_grid, dim3(256), 0, s, x, t.scale, t.shift, t.mean, residual, p.ep, p.seg_rows, p.spg, p.G, p.C, out, t.var_unb,
+                     f.running_mean, f.running_var, f.momentum, amax_out, (long long)(out_ld / 4));
+}
+
+struct NormFwdArgs {      // y: the tensor, or sl: the slabs whose sum the statistics pass leaves in sl.sum_out; f.partial / f.nb: the rows handed in, or null / 0
+  const float* y; SlabSrc sl; FinFwd f; void* workspace; const float* residual; float* out; long long out_ld; float* amax_out;
+};
+static void norm_fwd_launch(const NormRoute& r, const NormProblem& p, const NormFwdArgs& a, hipStream_t s) {
+  if (r.form == NormForm::Own) {
+    const OwnCommon oc{a.y, a.sl.slabs, a.sl.nslab, a.sl.stride, a.sl.bias, a.sl.sum_out, p.G, p.C, (int)p.rows_per_group, r.GS, r.cw, p.ep, a.amax_out};
+    const OwnFwd of{a.f.gamma, a.f.beta, a.f.running_mean, a.f.running_var, a.f.momentum, a.f.eps, a.residual, a.f.stats, a.out, a.out_ld};
+    hipLaunchKernelGGL(kOwnFwd[r.P >> 1], r.own_grid, dim3(kOwnThreads), 0, s, oc, of);
+    return;
+  }
+  const bool fused = r.form == NormForm::Fused;
+  const float* x = a.sl.slabs ? a.sl.sum_out : a.y;      // what an apply pass reads
+  FinFwd f = a.f;
+  if (!f.partial) { f.partial = reinterpret_cast<double*>(a.workspace); f.nb = r.nb; }
+  if (r.stats) col_partial_launch(0, r, p, a.y, nullptr, NormTable{}, reinterpret_cast<double*>(a.workspace), a.sl, fused ? a.amax_out : nullptr, s);
+  if (r.finalize) fwd_finalize_launch(r, p, f, a.out ? a.amax_out : nullptr, s);
+  if (fused)
+    hipLaunchKernelGGL(k_norm_apply_fin, r.fused_grid, dim3(256), 0, s, x, a.residual, p.ep, p.seg_rows, p.spg, p.G, p.C, p.rows_per_group, f, a.out, a.amax_out,
+                       a.out_ld);
+  else if (r.tail == NormTail::Apply) fwd_apply_launch(r, p, x, f, a.residual, a.out, a.out_ld, a.amax_out, s);
+  else if (r.tail == NormTail::Params) running_only_launch(p, f, s);
 }
 
 __global__ __launch_bounds__(256) void k_norm_bwd_params(const float* __restrict__ raw, int G, int C, float* __restrict__ dgamma,
@@ -1119,40 +1176,79 @@ __global__ __launch_bounds__(256) void k_norm_bwd_params(const float* __restrict
   }
 }
 
-// c1c2raw: float[4][G][C] -- the two means the apply pass subtracts, then the raw sums
+static void bwd_finalize_launch(const NormRoute& r, const NormProblem& p, const FinBwd& f, const NormCoef& k, float* amax_clear_or_null, hipStream_t s) {
+  hipLaunchKernelGGL(k_norm_bwd_finalize, r.fin_grid, dim3(kFinalizeThreads), 0, s, f.partial, f.nb, p.G, p.C, p.rows_per_group, f.dgamma, f.dbeta, f.accumulate,
+                     k.c1, k.c2, k.raw, amax_clear_or_null);
+}
+
+struct NormBwdArgs {      // da, or sl: the slabs whose sum the statistics pass leaves in sl.sum_out; f.partial / f.nb: as NormFwdArgs
+  const float* y; const float* da; SlabSrc sl; FinBwd f; const float* stats; void* workspace; float* dy; float* amax_out;
+};
+static void norm_bwd_launch(const NormRoute& r, const NormProblem& p, const NormBwdArgs& a, hipStream_t s) {
+  if (r.form == NormForm::Own) {
+    const OwnCommon oc{a.y, a.sl.slabs, a.sl.nslab, a.sl.stride, nullptr, a.sl.sum_out, p.G, p.C, (int)p.rows_per_group, r.GS, r.cw, p.ep, a.amax_out};
+    const OwnBwd ob{a.stats, a.da, a.f.dgamma, a.f.dbeta, a.f.accumulate, a.dy};
+    hipLaunchKernelGGL(kOwnBwd[r.P >> 1], r.own_grid, dim3(kOwnThreads), 0, s, oc, ob);
+    return;
+  }
+  const bool fused = r.form == NormForm::Fused;
+  const float* g = a.sl.slabs ? a.sl.sum_out : a.da;
+  const NormTable t = norm_table(a.stats, p.G, p.C);
+  const NormCoef k = norm_coef(reinterpret_cast<float*>(reinterpret_cast<char*>(a.workspace) + r.c1_offset), p.G, p.C);
+  FinBwd f = a.f;
+  if (!f.partial) { f.partial = reinterpret_cast<double*>(a.workspace); f.nb = r.nb; }
+  if (r.stats) col_partial_launch(1, r, p, a.y, a.da, t, reinterpret_cast<double*>(a.workspace), a.sl, fused ? a.amax_out : nullptr, s);
+  if (r.finalize) bwd_finalize_launch(r, p, f, k, a.amax_out, s);
+  if (fused)
+    hipLaunchKernelGGL(k_norm_bwd_apply_fin, r.fused_grid, dim3(256), 0, s, a.y, g, a.stats, p.ep, p.seg_rows, p.spg, p.G, p.C, p.rows_per_group, f, a.dy,
+                       a.amax_out);
+  else if (r.tail == NormTail::Apply)
+    hipLaunchKernelGGL(k_norm_bwd_apply, r.apply_grid, dim3(256), 0, s, a.y, g, t.scale, t.shift, t.mean, t.rstd, k.c1, k.c2, p.ep, p.seg_rows, p.spg, p.G, p.C,
+                       a.dy, k.raw, f.dgamma, f.dbeta, f.accumulate, a.amax_out);
+}
+
+// ---- finalize steps behind a statistics pass that somebody else made, in front of an apply pass of their own (csrc/gemm.hip, csrc/conv3.hip,
+// csrc/norm_res.hip): the chain of handed-in rows without an output tensor -- finalize, then the running statistics / parameter gradients
+static NormProblem plain_problem(int G, long long rows_per_group, int C, const float* chan_scale = nullptr, int act = ACT_NONE) {
+  return NormProblem{G, rows_per_group, C, NormEpilogue{chan_scale, nullptr, 1.f, rows_per_group, act, nullptr, 0.f}, rows_per_group, 1};
+}
+void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null) {
+  const NormProblem p = plain_problem(G, rows_per_group, C);
+  const NormRoute r = norm_route(NormDir::Fwd, NormSrc::Partial, p, false, running_mean != nullptr);
+  const FinFwd f{partial, nb, gamma, beta, running_mean, running_var, momentum, eps, stats};
+  if (r.finalize) fwd_finalize_launch(r, p, f, amax_clear_or_null, s);
+  if (r.tail == NormTail::Params) running_only_launch(p, f, s);
+}
 void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
                               float* c1c2raw, hipStream_t s, float* amax_clear_or_null) {
-  float *c1 = c1c2raw, *c2 = c1 + (long long)G * C, *raw = c2 + (long long)G * C;
-  if (!skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, dgamma, dbeta,
-                     accumulate, c1, c2, raw, amax_clear_or_null);
-  if (dgamma) hipLaunchKernelGGL(k_norm_bwd_params, dim3(1), dim3(256), 0, s, raw, G, C, dgamma, dbeta, accumulate);
+  const NormProblem p = plain_problem(G, rows_per_group, C);
+  const NormRoute r = norm_route(NormDir::Bwd, NormSrc::Partial, p, false, dgamma != nullptr);
+  const NormCoef k = norm_coef(c1c2raw, G, C);
+  if (r.finalize) bwd_finalize_launch(r, p, FinBwd{partial, nb, dgamma, dbeta, accumulate}, k, amax_clear_or_null, s);
+  if (r.tail == NormTail::Params) hipLaunchKernelGGL(k_norm_bwd_params, dim3(1), dim3(256), 0, s, k.raw, G, C, dgamma, dbeta, accumulate);
 }
 
 // ---- the per-sample streams a GroupNorm layer shares with the layers above (csrc/gnorm.hip; declarations: csrc/norm_shared.h): the same
-// kernels, launched with one group per sample.  GroupNorm forms its table and its backward coefficients in finalize kernels of its own.
+// launch sites with one group per sample.  GroupNorm forms its table and its backward coefficients in finalize kernels of its own.
+static NormRoute per_sample_route(const NormProblem& p) { return norm_route(NormDir::Fwd, NormSrc::Partial, p, false, false); }      // (its grids alone are used)
 int per_sample_stat_rows(long long rows_per_sample, int C) { return norm_blocks(rows_per_sample, C); }
-int per_sample_apply_blocks(long long rows_per_sample, int C, int N) { return apply_grid(rows_per_sample * (C / 4), N); }
+int per_sample_apply_blocks(long long rows_per_sample, int C, int N) { return apply_blocks(rows_per_sample * (C / 4), N); }
 
 void per_sample_stats_launch(const float* y, int N, long long rows_per_sample, int C, double* partial, hipStream_t s) {
-  const NormEpilogue ep{nullptr, nullptr, 1.f, rows_per_sample, ACT_NONE, nullptr, 0.f};
-  hipLaunchKernelGGL((k_col_partial<0>), dim3(norm_blocks(rows_per_sample, C), N), dim3(256), 0, s, y, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ep, rows_per_sample, 1, C, partial, SlabSrc{}, (float*)nullptr);
+  const NormProblem p = plain_problem(N, rows_per_sample, C);
+  col_partial_launch(0, per_sample_route(p), p, y, nullptr, NormTable{}, partial, SlabSrc{}, nullptr, s);
 }
-
 void per_sample_bwd_stats_launch(const float* y, const float* da, const float* table, int N, long long rows_per_sample, int C, int act,
                                  const float* chan_scale, double* partial, hipStream_t s) {
-  const NormEpilogue ep{chan_scale, nullptr, 1.f, rows_per_sample, act, nullptr, 0.f};
-  const float *mean = table, *rstd = table + (long long)N * C, *scale = table + 2LL * N * C, *shift = table + 3LL * N * C;
-  hipLaunchKernelGGL((k_col_partial<1>), dim3(norm_blocks(rows_per_sample, C), N), dim3(256), 0, s, y, da, scale, shift, mean, rstd, ep, rows_per_sample, 1,
-                     C, partial, SlabSrc{}, (float*)nullptr);
+  const NormProblem p = plain_problem(N, rows_per_sample, C, chan_scale, act);
+  col_partial_launch(1, per_sample_route(p), p, y, da, norm_table(table, N, C), partial, SlabSrc{}, nullptr, s);
 }
-
 void per_sample_apply_launch(const float* y, const float* table, int N, long long rows_per_sample, int C, int act, const float* chan_scale,
                              const float* residual, float* out, float* amax_out, hipStream_t s) {
-  const NormEpilogue ep{chan_scale, nullptr, 1.f, rows_per_sample, act, nullptr, 0.f};
-  const float *mean = table, *scale = table + 2LL * N * C, *shift = table + 3LL * N * C, *row4 = table + 4LL * N * C;
-  hipLaunchKernelGGL(k_norm_apply, dim3(apply_grid(rows_per_sample * (C / 4), N), N), dim3(256), 0, s, y, scale, shift, mean, residual, ep, rows_per_sample, 1,
-                     N, C, out, row4, (float*)nullptr, (float*)nullptr, 0.f, amax_out, (long long)(C / 4));
+  const NormProblem p = plain_problem(N, rows_per_sample, C, chan_scale, act);
+  const FinFwd f{nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, const_cast<float*>(table)};
+  fwd_apply_launch(per_sample_route(p), p, y, f, residual, out, C, amax_out, s);
 }
 
 }  // namespace bcp
@@ -1160,17 +1256,10 @@ void per_sample_apply_launch(const float* y, const float* table, int N, long lon
 using namespace bcp;
 
 extern "C" size_t bcp_norm_workspace_bytes(int G, long long rows_per_group, int C) {
-  if (G < 1 || C < 16 || rows_per_group < 1) return 0;
-  // per-block fp64 partials, then the two per-(g,c) backward means (c1, c2)
-  // (the slab-summing statistics pass of the deep levels uses more, smaller blocks: size the partial rows for whichever is larger)
-  const int nbmax = rows_per_group <= 4096 ? norm_blocks_slabs(rows_per_group, C, G, true) : norm_blocks(rows_per_group, C);
-  return (size_t)G * (nbmax + kMaxSamplesPerGroup) * C * 2 * sizeof(double) + (size_t)4 * G * C * sizeof(float);
-}
-
-static int check_norm_args(const char* fn, int G, long long rows_per_group, int C) {
-  BCP_REQUIRE(G >= 1 && rows_per_group >= 1, "%s: bad extents", fn);
-  BCP_REQUIRE(C >= 16 && C <= 1024 && (C & (C - 1)) == 0, "%s: C=%d unsupported (need a power of two in 16..1024)", fn, C);
-  return BCP_OK;
+  if (G < 1 || C < 16 || C > 1024 || rows_per_group < 1) return 0;      // (C > 1024: no thread-slot holds a row, and no entry point serves it)
+  // per-block fp64 partials, then c1c2raw, sized for whichever statistics pass leaves more rows (norm_route: every route fits)
+  const int rows = rows_per_group <= kSlabMaxRows ? slab_rows_max(rows_per_group, C, G) : norm_blocks(rows_per_group, C);
+  return (size_t)G * (rows + kMaxSamplesPerGroup) * C * 2 * sizeof(double) + (size_t)4 * G * C * sizeof(float);
 }
 
 extern "C" int bcp_norm_fwd(const float* y, int G, long long rows_per_group, int C, const float* gamma, const float* beta,
@@ -1178,51 +1267,18 @@ extern "C" int bcp_norm_fwd(const float* y, int G, long long rows_per_group, int
                             const float* chan_scale, long long rows_per_sample, const uint8_t* elem_mask, float elem_scale,
                             const unsigned long long* mask_seed /* nullable: evaluate the Dropout keep bits from this device seed */, float mask_p_keep,
                             const float* residual, float* stats /* [5][G][C]: mean, rstd, scale, beta, unbiased var */, void* workspace,
-                            const double* partial_in, int nb_in, float* out, long long out_ld /* row stride of out in floats; 0: C */,
+                            const double* partial_in /* nullable: the conv epilogue's (bcp_conv3_fwd_stats) */, int nb_in, float* out, long long out_ld /* row stride of out in floats; 0: C */,
                             float* amax_out /* nullable: max |out| (fp16 pre-scale of the conv that reads it) */, void* stream) {
-  if (int rc = check_norm_args("bcp_norm_fwd", G, rows_per_group, C)) return rc;
+  NormProblem p;
+  if (int rc = norm_problem("bcp_norm_fwd", G, rows_per_group, C, NormEpilogue{chan_scale, elem_mask, elem_scale, rows_per_sample, act, mask_seed, mask_p_keep}, p)) return rc;
   if (out_ld == 0) out_ld = C;
   BCP_REQUIRE(out_ld >= C && (out_ld & 3) == 0, "bcp_norm_fwd: out_ld=%lld (need a multiple of 4 >= C)", out_ld);
   BCP_REQUIRE(y && stats && workspace, "bcp_norm_fwd: null pointer");
   BCP_REQUIRE(aligned16(y) && (!out || aligned16(out)) && aligned16(stats), "bcp_norm_fwd: alignment");
   BCP_REQUIRE(out || !residual, "bcp_norm_fwd: statistics-only mode (out = NULL) takes no residual");
-  hipStream_t s = (hipStream_t)stream;
-  NormEpilogue ep{chan_scale, elem_mask, elem_scale, rows_per_sample > 0 ? rows_per_sample : rows_per_group, act, mask_seed, mask_p_keep};
-  BCP_REQUIRE(!chan_scale || (rows_per_group % ep.rows_per_sample == 0 && rows_per_group / ep.rows_per_sample <= kMaxSamplesPerGroup),
-              "bcp_norm_fwd: a group must hold 1..%d whole samples", kMaxSamplesPerGroup);
-  const Segs sg = make_segs(G, rows_per_group, C, ep);
-  const int nseg = G * sg.spg, nb = sg.nbps * sg.spg;
-  double* partial = reinterpret_cast<double*>(workspace);
-  float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
-  float* var_unb = stats + 4LL * G * C;
-  int own_cw = 0;
-  if (const int GS = (out && !partial_in) ? own_gs(G, rows_per_group, C, running_mean != nullptr, own_cw) : 0) {      // (round 6) the smallest levels: ONE launch
-    const OwnCommon oc{y, nullptr, 0, 0, nullptr, nullptr, G, C, (int)rows_per_group, GS, own_cw, ep, amax_out};
-    const OwnFwd of{gamma, beta, running_mean, running_var, momentum, eps, residual, stats, out, out_ld};
-    BCP_OWN_LAUNCH(k_norm_own_fwd, rows_per_group, GS, G, C, s, oc, of);
-    BCP_CHECK_LAUNCH("bcp_norm_fwd");
-    return BCP_OK;
-  }
-  const bool fused = out && !partial_in && fin_fused_ok(nb, C);      // (round 6) the apply pass finalises the statistics itself: no finalize launch
-  if (partial_in) {   // statistics partials were produced by the conv epilogue (bcp_conv3_fwd_stats)
-    if (!skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial_in, nb_in, G, C, rows_per_group, gamma, beta,
-                       running_mean, running_var, momentum, eps, mean, rstd, scale, shift, var_unb, out ? amax_out : (float*)nullptr);
-  } else {
-    hipLaunchKernelGGL((k_col_partial<0>), dim3(sg.nbps, nseg), dim3(256), 0, s, y, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ep, sg.seg_rows, sg.spg, C, partial, SlabSrc{},
-                       fused ? amax_out : (float*)nullptr);
-    if (!fused && !skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, gamma, beta,
-                       running_mean, running_var, momentum, eps, mean, rstd, scale, shift, var_unb, out ? amax_out : (float*)nullptr);
-  }
-  if (fused)
-    hipLaunchKernelGGL(k_norm_apply_fin, fin_grid(sg.seg_rows, nseg, C, running_mean != nullptr), dim3(256), 0, s, y, residual, ep, sg.seg_rows, sg.spg, G, C, rows_per_group,
-                       FinFwd{partial, nb, gamma, beta, running_mean, running_var, momentum, eps, stats}, out, amax_out, out_ld);
-  else if (out && skip_app(rows_per_group)) {}
-  else if (out)
-    hipLaunchKernelGGL(k_norm_apply, dim3(apply_grid(sg.seg_rows * (C / 4), nseg), nseg), dim3(256), 0, s, y, scale, shift, mean, residual,
-                       ep, sg.seg_rows, sg.spg, G, C, out, var_unb, running_mean, running_var, momentum, amax_out, (long long)(out_ld / 4));
-  else if (running_mean)   // statistics only: the consumer applies the normalisation itself (bcp_pw16_fwd_norm); the apply pass also carries the running-statistics update
-    hipLaunchKernelGGL(k_norm_running_only, dim3(1), dim3(256), 0, s, mean, var_unb, G, C, running_mean, running_var, momentum);
+  const NormRoute r = norm_route(NormDir::Fwd, partial_in ? NormSrc::Partial : NormSrc::Tensor, p, out != nullptr, running_mean != nullptr);
+  norm_fwd_launch(r, p, NormFwdArgs{y, SlabSrc{}, FinFwd{partial_in, partial_in ? nb_in : 0, gamma, beta, running_mean, running_var, momentum, eps, stats}, workspace,
+                                    residual, out, out_ld, amax_out}, (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_norm_fwd");
   return BCP_OK;
 }
@@ -1230,45 +1286,14 @@ extern "C" int bcp_norm_fwd(const float* y, int G, long long rows_per_group, int
 extern "C" int bcp_norm_bwd(const float* y, const float* da, int G, long long rows_per_group, int C, const float* stats,
                             int act, const float* chan_scale, long long rows_per_sample, const uint8_t* elem_mask,
                             float elem_scale, const unsigned long long* mask_seed, float mask_p_keep, float* dgamma, float* dbeta, int accumulate, void* workspace,
-                            const double* partial_in, int nb_in, float* dy, float* amax_out /* nullable: max |dy| */, void* stream) {
-  if (int rc = check_norm_args("bcp_norm_bwd", G, rows_per_group, C)) return rc;
+                            const double* partial_in /* nullable: (sum dz, sum dz * xhat) rows of the caller's */, int nb_in, float* dy, float* amax_out /* nullable: max |dy| */, void* stream) {
+  NormProblem p;
+  if (int rc = norm_problem("bcp_norm_bwd", G, rows_per_group, C, NormEpilogue{chan_scale, elem_mask, elem_scale, rows_per_sample, act, mask_seed, mask_p_keep}, p)) return rc;
   BCP_REQUIRE(y && da && stats && workspace && dy, "bcp_norm_bwd: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  NormEpilogue ep{chan_scale, elem_mask, elem_scale, rows_per_sample > 0 ? rows_per_sample : rows_per_group, act, mask_seed, mask_p_keep};
-  BCP_REQUIRE(!chan_scale || (rows_per_group % ep.rows_per_sample == 0 && rows_per_group / ep.rows_per_sample <= kMaxSamplesPerGroup),
-              "bcp_norm_bwd: a group must hold 1..%d whole samples", kMaxSamplesPerGroup);
-  const Segs sg = make_segs(G, rows_per_group, C, ep);
-  const int nseg = G * sg.spg, nb = sg.nbps * sg.spg;
-  double* partial = reinterpret_cast<double*>(workspace);
-  const float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
-  // c1/c2 live behind the partials in the workspace
-  float* c1 = reinterpret_cast<float*>(partial + (size_t)G * (norm_blocks(rows_per_group, C) + kMaxSamplesPerGroup) * C * 2);
-  float* c2 = c1 + (long long)G * C;
-  float* raw = c2 + (long long)G * C;
-  int own_cw = 0;
-  if (const int GS = !partial_in ? own_gs(G, rows_per_group, C, dgamma != nullptr, own_cw) : 0) {
-    const OwnCommon oc{y, nullptr, 0, 0, nullptr, nullptr, G, C, (int)rows_per_group, GS, own_cw, ep, amax_out};
-    const OwnBwd ob{stats, da, dgamma, dbeta, accumulate, dy};
-    BCP_OWN_LAUNCH(k_norm_own_bwd, rows_per_group, GS, G, C, s, oc, ob);
-    BCP_CHECK_LAUNCH("bcp_norm_bwd");
-    return BCP_OK;
-  }
-  const bool fused = !partial_in && fin_fused_ok(nb, C);
-  if (partial_in) {   // (sum dz, sum dz * xhat) partials handed in by the caller (no kernel of the library produces them any more)
-    BCP_REQUIRE(!chan_scale && !elem_mask && !mask_seed && nb_in > 0, "bcp_norm_bwd: fused statistics do not cover dropout epilogues");
-    if (!skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial_in, nb_in, G, C, rows_per_group, dgamma,
-                       dbeta, accumulate, c1, c2, raw, amax_out);
-  } else {
-    if (!skip_bstat(rows_per_group)) hipLaunchKernelGGL((k_col_partial<1>), dim3(sg.nbps, nseg), dim3(256), 0, s, y, da, scale, shift, mean, rstd, ep, sg.seg_rows, sg.spg,
-                       C, partial, SlabSrc{}, fused ? amax_out : (float*)nullptr);
-    if (!fused && !skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, dgamma,
-                       dbeta, accumulate, c1, c2, raw, amax_out);
-  }
-  if (fused)
-    hipLaunchKernelGGL(k_norm_bwd_apply_fin, fin_grid(sg.seg_rows, nseg, C, dgamma != nullptr), dim3(256), 0, s, y, da, stats, ep, sg.seg_rows, sg.spg, G, C, rows_per_group,
-                       FinBwd{partial, nb, dgamma, dbeta, accumulate}, dy, amax_out);
-  else if (!skip_app(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_apply, dim3(apply_grid(sg.seg_rows * (C / 4), nseg), nseg), dim3(256), 0, s, y, da, scale, shift, mean,
-                     rstd, c1, c2, ep, sg.seg_rows, sg.spg, G, C, dy, raw, dgamma, dbeta, accumulate, amax_out);
+  BCP_REQUIRE(!partial_in || (!chan_scale && !elem_mask && !mask_seed && nb_in > 0), "bcp_norm_bwd: fused statistics do not cover dropout epilogues");
+  const NormRoute r = norm_route(NormDir::Bwd, partial_in ? NormSrc::Partial : NormSrc::Tensor, p, true, dgamma != nullptr);
+  norm_bwd_launch(r, p, NormBwdArgs{y, da, SlabSrc{}, FinBwd{partial_in, partial_in ? nb_in : 0, dgamma, dbeta, accumulate}, stats, workspace, dy, amax_out},
+                  (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_norm_bwd");
   return BCP_OK;
 }
@@ -1276,7 +1301,7 @@ extern "C" int bcp_norm_bwd(const float* y, const float* da, int G, long long ro
 // ---- deep levels: the producing conv left its raw split-K slabs (bcp_conv3_fwd_raw); the statistics pass sums them on its way in
 // (k_col_partial<MODE, SL = true>) and writes the sum once for the apply pass.  Bit-identical to k_b6_sum_slabs + bcp_norm_fwd / _bwd.
 extern "C" int bcp_norm_slabs_ok(int G, long long rows_per_group, int C) {
-  return (options().norm_slabs != 0 && G >= 1 && rows_per_group >= 1 && rows_per_group <= 4096 && C >= 16 && C <= 1024 && (C & (C - 1)) == 0) ? 1 : 0;
+  return (options().norm_slabs != 0 && G >= 1 && rows_per_group >= 1 && rows_per_group <= kSlabMaxRows && C >= 16 && C <= 1024 && (C & (C - 1)) == 0) ? 1 : 0;
 }
 
 extern "C" int bcp_norm_fwd_slabs(const float* slabs, int nslab, long long slab_stride, const float* bias, float* ysum, int G,
@@ -1285,45 +1310,16 @@ extern "C" int bcp_norm_fwd_slabs(const float* slabs, int nslab, long long slab_
                                   const uint8_t* elem_mask, float elem_scale, const unsigned long long* mask_seed, float mask_p_keep,
                                   const float* residual, float* stats, void* workspace, float* out,
                                   float* amax_out, void* stream) {
-  if (int rc = check_norm_args("bcp_norm_fwd_slabs", G, rows_per_group, C)) return rc;
-  BCP_REQUIRE(rows_per_group <= 4096, "bcp_norm_fwd_slabs: rows_per_group=%lld > 4096 (check bcp_norm_slabs_ok)", rows_per_group);
+  NormProblem p;
+  if (int rc = norm_problem("bcp_norm_fwd_slabs", G, rows_per_group, C, NormEpilogue{chan_scale, elem_mask, elem_scale, rows_per_sample, act, mask_seed, mask_p_keep}, p)) return rc;
+  BCP_REQUIRE(rows_per_group <= kSlabMaxRows, "bcp_norm_fwd_slabs: rows_per_group=%lld > %lld (check bcp_norm_slabs_ok)", rows_per_group, kSlabMaxRows);
   BCP_REQUIRE(slabs && ysum && stats && workspace && nslab >= 1 && nslab <= 64, "bcp_norm_fwd_slabs: null pointer / bad slab count");
   BCP_REQUIRE(aligned16(slabs) && aligned16(ysum) && (!out || aligned16(out)) && aligned16(stats) && (slab_stride & 3) == 0 && (!bias || aligned16(bias)),
               "bcp_norm_fwd_slabs: alignment");
   BCP_REQUIRE(out || !residual, "bcp_norm_fwd_slabs: statistics-only mode (out = NULL) takes no residual");
-  hipStream_t s = (hipStream_t)stream;
-  NormEpilogue ep{chan_scale, elem_mask, elem_scale, rows_per_sample > 0 ? rows_per_sample : rows_per_group, act, mask_seed, mask_p_keep};
-  BCP_REQUIRE(!chan_scale || (rows_per_group % ep.rows_per_sample == 0 && rows_per_group / ep.rows_per_sample <= kMaxSamplesPerGroup),
-              "bcp_norm_fwd_slabs: a group must hold 1..%d whole samples", kMaxSamplesPerGroup);
-  const Segs sg = make_segs(G, rows_per_group, C, ep, norm_blocks_slabs(rows_per_group, C, G));
-  const int nseg = G * sg.spg, nb = sg.nbps * sg.spg;
-  double* partial = reinterpret_cast<double*>(workspace);
-  float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
-  float* var_unb = stats + 4LL * G * C;
-  const SlabSrc sl{slabs, nslab, slab_stride, bias, ysum};
-  int own_cw = 0;
-  if (const int GS = out ? own_gs(G, rows_per_group, C, running_mean != nullptr, own_cw) : 0) {
-    const OwnCommon oc{nullptr, slabs, nslab, slab_stride, bias, ysum, G, C, (int)rows_per_group, GS, own_cw, ep, amax_out};
-    const OwnFwd of{gamma, beta, running_mean, running_var, momentum, eps, residual, stats, out, (long long)C};
-    BCP_OWN_LAUNCH(k_norm_own_fwd, rows_per_group, GS, G, C, s, oc, of);
-    BCP_CHECK_LAUNCH("bcp_norm_fwd_slabs");
-    return BCP_OK;
-  }
-  const bool fused = out && fin_fused_ok(nb, C);
-  hipLaunchKernelGGL((k_col_partial<0, true>), dim3(sg.nbps, nseg), dim3(256), 0, s, (const float*)nullptr, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, ep, sg.seg_rows, sg.spg, C, partial, sl,
-                     fused ? amax_out : (float*)nullptr);
-  if (!fused && !skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, gamma, beta,
-                     running_mean, running_var, momentum, eps, mean, rstd, scale, shift, var_unb, out ? amax_out : (float*)nullptr);
-  if (fused)
-    hipLaunchKernelGGL(k_norm_apply_fin, fin_grid(sg.seg_rows, nseg, C, running_mean != nullptr), dim3(256), 0, s, ysum, residual, ep, sg.seg_rows, sg.spg, G, C, rows_per_group,
-                       FinFwd{partial, nb, gamma, beta, running_mean, running_var, momentum, eps, stats}, out, amax_out, (long long)C);
-  else if (out && skip_app(rows_per_group)) {}
-  else if (out)
-    hipLaunchKernelGGL(k_norm_apply, dim3(apply_grid(sg.seg_rows * (C / 4), nseg), nseg), dim3(256), 0, s, ysum, scale, shift, mean, residual,
-                       ep, sg.seg_rows, sg.spg, G, C, out, var_unb, running_mean, running_var, momentum, amax_out, (long long)(C / 4));
-  else if (running_mean)
-    hipLaunchKernelGGL(k_norm_running_only, dim3(1), dim3(256), 0, s, mean, var_unb, G, C, running_mean, running_var, momentum);
+  const NormRoute r = norm_route(NormDir::Fwd, NormSrc::Slabs, p, out != nullptr, running_mean != nullptr);
+  norm_fwd_launch(r, p, NormFwdArgs{nullptr, SlabSrc{slabs, nslab, slab_stride, bias, ysum}, FinFwd{nullptr, 0, gamma, beta, running_mean, running_var, momentum, eps, stats},
+                                    workspace, residual, out, (long long)C, amax_out}, (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_norm_fwd_slabs");
   return BCP_OK;
 }
@@ -1333,41 +1329,16 @@ extern "C" int bcp_norm_bwd_slabs(const float* y, const float* da_slabs, int nsl
                                   long long rows_per_sample, const uint8_t* elem_mask, float elem_scale, const unsigned long long* mask_seed,
                                   float mask_p_keep, float* dgamma, float* dbeta,
                                   int accumulate, void* workspace, float* dy, float* amax_out, void* stream) {
-  if (int rc = check_norm_args("bcp_norm_bwd_slabs", G, rows_per_group, C)) return rc;
-  BCP_REQUIRE(rows_per_group <= 4096, "bcp_norm_bwd_slabs: rows_per_group=%lld > 4096 (check bcp_norm_slabs_ok)", rows_per_group);
+  NormProblem p;
+  if (int rc = norm_problem("bcp_norm_bwd_slabs", G, rows_per_group, C, NormEpilogue{chan_scale, elem_mask, elem_scale, rows_per_sample, act, mask_seed, mask_p_keep}, p)) return rc;
+  BCP_REQUIRE(rows_per_group <= kSlabMaxRows, "bcp_norm_bwd_slabs: rows_per_group=%lld > %lld (check bcp_norm_slabs_ok)", rows_per_group, kSlabMaxRows);
   BCP_REQUIRE(y && da_slabs && da_sum && stats && workspace && dy && nslab >= 1 && nslab <= 64, "bcp_norm_bwd_slabs: null pointer / bad slab count");
   BCP_REQUIRE(aligned16(y) && aligned16(da_slabs) && aligned16(dy) && aligned16(da_sum) && (slab_stride & 3) == 0, "bcp_norm_bwd_slabs: alignment");
   BCP_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "bcp_norm_bwd_slabs: dgamma and dbeta come together");
-  hipStream_t s = (hipStream_t)stream;
-  NormEpilogue ep{chan_scale, elem_mask, elem_scale, rows_per_sample > 0 ? rows_per_sample : rows_per_group, act, mask_seed, mask_p_keep};
-  BCP_REQUIRE(!chan_scale || (rows_per_group % ep.rows_per_sample == 0 && rows_per_group / ep.rows_per_sample <= kMaxSamplesPerGroup),
-              "bcp_norm_bwd_slabs: a group must hold 1..%d whole samples", kMaxSamplesPerGroup);
-  const Segs sg = make_segs(G, rows_per_group, C, ep, norm_blocks_slabs(rows_per_group, C, G));
-  const int nseg = G * sg.spg, nb = sg.nbps * sg.spg;
-  double* partial = reinterpret_cast<double*>(workspace);
-  const float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
-  float* c1 = reinterpret_cast<float*>(partial + (size_t)G * (norm_blocks_slabs(rows_per_group, C, G) + kMaxSamplesPerGroup) * C * 2);
-  float* c2 = c1 + (long long)G * C;
-  float* raw = c2 + (long long)G * C;
-  const SlabSrc sl{da_slabs, nslab, slab_stride, nullptr, da_sum};
-  int own_cw = 0;
-  if (const int GS = own_gs(G, rows_per_group, C, dgamma != nullptr, own_cw)) {
-    const OwnCommon oc{y, da_slabs, nslab, slab_stride, nullptr, da_sum, G, C, (int)rows_per_group, GS, own_cw, ep, amax_out};
-    const OwnBwd ob{stats, nullptr, dgamma, dbeta, accumulate, dy};
-    BCP_OWN_LAUNCH(k_norm_own_bwd, rows_per_group, GS, G, C, s, oc, ob);
-    BCP_CHECK_LAUNCH("bcp_norm_bwd_slabs");
-    return BCP_OK;
-  }
-  const bool fused = fin_fused_ok(nb, C);
-  hipLaunchKernelGGL((k_col_partial<1, true>), dim3(sg.nbps, nseg), dim3(256), 0, s, y, (const float*)nullptr, scale, shift, mean, rstd, ep,
-                     sg.seg_rows, sg.spg, C, partial, sl, fused ? amax_out : (float*)nullptr);
-  if (!fused && !skip_fin(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_finalize, dim3(G * (C / 16)), dim3(kFinalizeThreads), 0, s, partial, nb, G, C, rows_per_group, dgamma,
-                     dbeta, accumulate, c1, c2, raw, amax_out);
-  if (fused)
-    hipLaunchKernelGGL(k_norm_bwd_apply_fin, fin_grid(sg.seg_rows, nseg, C, dgamma != nullptr), dim3(256), 0, s, y, da_sum, stats, ep, sg.seg_rows, sg.spg, G, C, rows_per_group,
-                       FinBwd{partial, nb, dgamma, dbeta, accumulate}, dy, amax_out);
-  else if (!skip_app(rows_per_group)) hipLaunchKernelGGL(k_norm_bwd_apply, dim3(apply_grid(sg.seg_rows * (C / 4), nseg), nseg), dim3(256), 0, s, y, da_sum, scale, shift, mean,
-                     rstd, c1, c2, ep, sg.seg_rows, sg.spg, G, C, dy, raw, dgamma, dbeta, accumulate, amax_out);
+  const NormRoute r = norm_route(NormDir::Bwd, NormSrc::Slabs, p, true, dgamma != nullptr);
+  norm_bwd_launch(r, p, NormBwdArgs{y, nullptr, SlabSrc{da_slabs, nslab, slab_stride, nullptr, da_sum}, FinBwd{nullptr, 0, dgamma, dbeta, accumulate}, stats, workspace,
+                                    dy, amax_out}, (hipStream_t)stream);
   BCP_CHECK_LAUNCH("bcp_norm_bwd_slabs");
   return BCP_OK;
 }
+

@@ -15,12 +15,6 @@
 
 namespace bcp {
 
-// csrc/norm.hip: the finalize launches between a statistics pass and an apply pass
-void norm_fwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, const float* gamma, const float* beta,
-                              float* running_mean, float* running_var, float momentum, float eps, float* stats, hipStream_t s, float* amax_clear_or_null);
-void norm_bwd_finalize_launch(const double* partial, int nb, int G, int C, long long rows_per_group, float* dgamma, float* dbeta, int accumulate,
-                              float* c1c2raw, hipStream_t s, float* amax_clear_or_null);
-
 // the residual of the four channels at float4 index i (row = (i - col) / C4): its own float4, or the row's single value in all four
 template <bool RB>
 __device__ __forceinline__ float4 ld_res(const float* __restrict__ res, long long i, int col, int c4sh) {
@@ -257,63 +251,48 @@ __global__ __launch_bounds__(256) void k_norm_eval_res(const float* __restrict__
   }
 }
 
-struct ResSegs { long long seg_rows; int spg; int nbps; };
-static constexpr int kResMaxSamplesPerGroup = 64;      // (csrc/norm.hip kMaxSamplesPerGroup: what bcp_norm_workspace_bytes sizes the partial rows for)
-static inline ResSegs res_segs(long long rows_per_group, int C, const float* chan_scale, long long rows_per_sample) {
-  ResSegs sg{rows_per_group, 1, per_sample_stat_rows(rows_per_group, C)};
-  if (chan_scale && rows_per_sample < rows_per_group) {
-    sg.seg_rows = rows_per_sample;
-    sg.spg = (int)(rows_per_group / rows_per_sample);
-    sg.nbps = sg.nbps / sg.spg < 1 ? 1 : sg.nbps / sg.spg;
-  }
-  return sg;
-}
+// the instances by the residual's width: [res_channels == 1]
+static const decltype(&k_norm_apply_res<false>) kApplyRes[2] = {k_norm_apply_res<false>, k_norm_apply_res<true>};
+static const decltype(&k_col_partial_res<false>) kColPartialRes[2] = {k_col_partial_res<false>, k_col_partial_res<true>};
+static const decltype(&k_norm_bwd_apply_res<false>) kBwdApplyRes[2] = {k_norm_bwd_apply_res<false>, k_norm_bwd_apply_res<true>};
+static const decltype(&k_norm_eval_res<false>) kEvalRes[2] = {k_norm_eval_res<false>, k_norm_eval_res<true>};
 
-}  // namespace bcp
-
-using namespace bcp;
-
-static int check_res_args(const char* fn, int G, long long rows_per_group, int C, const float* res, int res_channels) {
-  BCP_REQUIRE(G >= 1 && rows_per_group >= 1, "%s: bad extents", fn);
-  BCP_REQUIRE(C >= 16 && C <= 1024 && (C & (C - 1)) == 0, "%s: C=%d unsupported (need a power of two in 16..1024)", fn, C);
+// norm_problem() and the residual's own checks
+static int res_problem(const char* fn, int G, long long rows_per_group, int C, const float* chan_scale, long long rows_per_sample, int act, const float* res,
+                       int res_channels, NormProblem& p) {
+  if (int rc = norm_problem(fn, G, rows_per_group, C, NormEpilogue{chan_scale, nullptr, 1.f, rows_per_sample, act, nullptr, 0.f}, p)) return rc;
   BCP_REQUIRE(res != nullptr, "%s: null residual (bcp_norm_fwd / _bwd / _eval are the entry points without one)", fn);
   BCP_REQUIRE(res_channels == C || res_channels == 1, "%s: res_channels=%d (need C=%d, or 1 for a broadcast residual)", fn, res_channels, C);
   BCP_REQUIRE(res_channels == 1 ? (reinterpret_cast<uintptr_t>(res) & 3u) == 0 : aligned16(res), "%s: alignment of the residual", fn);
   return BCP_OK;
 }
 
+}  // namespace bcp
+
+using namespace bcp;
+
 extern "C" int bcp_norm_fwd_res(const float* y, int G, long long rows_per_group, int C, const float* gamma, const float* beta, float* running_mean,
                                 float* running_var, float momentum, float eps, int act, const float* chan_scale, long long rows_per_sample,
                                 const float* res_pre, int res_channels, float* stats, void* workspace, const double* partial_in, int nb_in,
                                 float* out, float* amax_out, void* stream) {
   BCP_REQUIRE(out != nullptr, "bcp_norm_fwd_res: statistics-only mode (out = NULL) takes no residual: use bcp_norm_fwd");
-  if (int rc = check_res_args("bcp_norm_fwd_res", G, rows_per_group, C, res_pre, res_channels)) return rc;
+  NormProblem p;
+  if (int rc = res_problem("bcp_norm_fwd_res", G, rows_per_group, C, chan_scale, rows_per_sample, act, res_pre, res_channels, p)) return rc;
   BCP_REQUIRE(y && stats && workspace, "bcp_norm_fwd_res: null pointer");
   BCP_REQUIRE(aligned16(y) && aligned16(out) && aligned16(stats) && aligned16(workspace) && (!chan_scale || aligned16(chan_scale)) &&
                   (!gamma || aligned16(gamma)) && (!beta || aligned16(beta)), "bcp_norm_fwd_res: alignment");
   BCP_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bcp_norm_fwd_res: running_mean and running_var come together");
   BCP_REQUIRE(!partial_in || nb_in > 0, "bcp_norm_fwd_res: partial_in without rows");
-  const long long rps = rows_per_sample > 0 ? rows_per_sample : rows_per_group;
-  BCP_REQUIRE(!chan_scale || (rows_per_group % rps == 0 && rows_per_group / rps <= kResMaxSamplesPerGroup),
-              "bcp_norm_fwd_res: a group must hold 1..%d whole samples", kResMaxSamplesPerGroup);
   hipStream_t s = (hipStream_t)stream;
-  const ResSegs sg = res_segs(rows_per_group, C, chan_scale, rps);
-  const int nseg = G * sg.spg;
-  double* partial = reinterpret_cast<double*>(workspace);
-  const float *mean = stats, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
+  const NormRoute r = norm_route(NormDir::Fwd, partial_in ? NormSrc::Partial : NormSrc::Tensor, p, true, running_mean != nullptr);
+  const NormTable t = norm_table(stats, G, C);
   // statistics of y: norm.hip's pass (one partial-row block per group), or the producer's rows; finalize (clears the |max| slots) + running statistics
-  int nb = nb_in;
-  if (!partial_in) {
-    per_sample_stats_launch(y, G, rows_per_group, C, partial, s);
-    nb = per_sample_stat_rows(rows_per_group, C);
-  }
-  norm_fwd_finalize_launch(partial_in ? partial_in : partial, nb, G, C, rows_per_group, gamma, beta, running_mean, running_var, momentum, eps, stats, s,
-                           amax_out);
-  const dim3 grid(per_sample_apply_blocks(sg.seg_rows, C, nseg), nseg);
-  if (res_channels == 1)
-    hipLaunchKernelGGL((k_norm_apply_res<true>), grid, dim3(256), 0, s, y, scale, shift, mean, res_pre, chan_scale, rps, act, sg.seg_rows, sg.spg, C, out, amax_out);
-  else
-    hipLaunchKernelGGL((k_norm_apply_res<false>), grid, dim3(256), 0, s, y, scale, shift, mean, res_pre, chan_scale, rps, act, sg.seg_rows, sg.spg, C, out, amax_out);
+  double* partial = reinterpret_cast<double*>(workspace);
+  if (!partial_in) per_sample_stats_launch(y, G, rows_per_group, C, partial, s);
+  norm_fwd_finalize_launch(partial_in ? partial_in : partial, partial_in ? nb_in : per_sample_stat_rows(rows_per_group, C), G, C, rows_per_group, gamma, beta,
+                           running_mean, running_var, momentum, eps, stats, s, amax_out);
+  hipLaunchKernelGGL(kApplyRes[res_channels == 1], r.apply_grid, dim3(256), 0, s, y, t.scale, t.shift, t.mean, res_pre,
+                     chan_scale, p.ep.rows_per_sample, act, p.seg_rows, p.spg, C, out, amax_out);
   BCP_CHECK_LAUNCH("bcp_norm_fwd_res");
   return BCP_OK;
 }
@@ -321,52 +300,42 @@ extern "C" int bcp_norm_fwd_res(const float* y, int G, long long rows_per_group,
 extern "C" int bcp_norm_bwd_res(const float* y, const float* da, const float* res_pre, int res_channels, int G, long long rows_per_group, int C,
                                 const float* stats, int act, const float* chan_scale, long long rows_per_sample, float* dgamma, float* dbeta,
                                 int accumulate, void* workspace, float* dy, float* dres, float* amax_out, void* stream) {
-  if (int rc = check_res_args("bcp_norm_bwd_res", G, rows_per_group, C, res_pre, res_channels)) return rc;
+  NormProblem p;
+  if (int rc = res_problem("bcp_norm_bwd_res", G, rows_per_group, C, chan_scale, rows_per_sample, act, res_pre, res_channels, p)) return rc;
   BCP_REQUIRE(y && da && stats && workspace && dy, "bcp_norm_bwd_res: null pointer");
   BCP_REQUIRE(aligned16(y) && aligned16(da) && aligned16(stats) && aligned16(workspace) && aligned16(dy) && (!dres || aligned16(dres)) &&
                   (!chan_scale || aligned16(chan_scale)), "bcp_norm_bwd_res: alignment");
   BCP_REQUIRE((dgamma == nullptr) == (dbeta == nullptr), "bcp_norm_bwd_res: dgamma and dbeta come together");
   BCP_REQUIRE(!(dres && res_channels == 1), "bcp_norm_bwd_res: the gradient of a broadcast residual is not produced (dres must be NULL for res_channels = 1)");
-  const long long rps = rows_per_sample > 0 ? rows_per_sample : rows_per_group;
-  BCP_REQUIRE(!chan_scale || (rows_per_group % rps == 0 && rows_per_group / rps <= kResMaxSamplesPerGroup),
-              "bcp_norm_bwd_res: a group must hold 1..%d whole samples", kResMaxSamplesPerGroup);
   hipStream_t s = (hipStream_t)stream;
-  const ResSegs sg = res_segs(rows_per_group, C, chan_scale, rps);
-  const int nseg = G * sg.spg, nb = sg.nbps * sg.spg;
+  // the chain of bcp_norm_bwd over the tensor, with the streams that read r: its grids, its partial rows and its c1c2raw behind them
+  const NormRoute r = norm_route(NormDir::Bwd, NormSrc::Tensor, p, true, dgamma != nullptr);
+  const NormTable t = norm_table(stats, G, C);
   double* partial = reinterpret_cast<double*>(workspace);
-  const float *mean = stats, *rstd = stats + (long long)G * C, *scale = stats + 2LL * G * C, *shift = stats + 3LL * G * C;
-  // c1 / c2 / the raw sums live behind the partial rows, where bcp_norm_bwd keeps them
-  float* c1 = reinterpret_cast<float*>(partial + (size_t)G * (per_sample_stat_rows(rows_per_group, C) + kResMaxSamplesPerGroup) * C * 2);
-  float* c2 = c1 + (long long)G * C;
-  const dim3 sgrid(sg.nbps, nseg), agrid(per_sample_apply_blocks(sg.seg_rows, C, nseg), nseg);
-  if (res_channels == 1)
-    hipLaunchKernelGGL((k_col_partial_res<true>), sgrid, dim3(256), 0, s, y, da, res_pre, scale, shift, mean, rstd, chan_scale, rps, act, sg.seg_rows, sg.spg, C, partial);
-  else
-    hipLaunchKernelGGL((k_col_partial_res<false>), sgrid, dim3(256), 0, s, y, da, res_pre, scale, shift, mean, rstd, chan_scale, rps, act, sg.seg_rows, sg.spg, C, partial);
-  norm_bwd_finalize_launch(partial, nb, G, C, rows_per_group, dgamma, dbeta, accumulate, c1, s, amax_out);
-  if (res_channels == 1)
-    hipLaunchKernelGGL((k_norm_bwd_apply_res<true>), agrid, dim3(256), 0, s, y, da, res_pre, scale, shift, mean, rstd, c1, c2, chan_scale, rps, act, sg.seg_rows,
-                       sg.spg, C, dy, dres, amax_out);
-  else
-    hipLaunchKernelGGL((k_norm_bwd_apply_res<false>), agrid, dim3(256), 0, s, y, da, res_pre, scale, shift, mean, rstd, c1, c2, chan_scale, rps, act, sg.seg_rows,
-                       sg.spg, C, dy, dres, amax_out);
+  const NormCoef k = norm_coef(reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + r.c1_offset), G, C);
+  const int rb = res_channels == 1;
+  hipLaunchKernelGGL(kColPartialRes[rb], r.stat_grid, dim3(256), 0, s, y, da, res_pre, t.scale, t.shift, t.mean,
+                     t.rstd, chan_scale, p.ep.rows_per_sample, act, p.seg_rows, p.spg, C, partial);
+  norm_bwd_finalize_launch(partial, r.nb, G, C, rows_per_group, dgamma, dbeta, accumulate, k.c1, s, amax_out);
+  hipLaunchKernelGGL(kBwdApplyRes[rb], r.apply_grid, dim3(256), 0, s, y, da, res_pre, t.scale, t.shift, t.mean,
+                     t.rstd, k.c1, k.c2, chan_scale, p.ep.rows_per_sample, act, p.seg_rows, p.spg, C, dy, dres, amax_out);
   BCP_CHECK_LAUNCH("bcp_norm_bwd_res");
   return BCP_OK;
 }
 
 extern "C" int bcp_norm_eval_res(const float* y, long long rows, int C, const float* gamma, const float* beta, const float* running_mean,
                                  const float* running_var, float eps, int act, const float* res_pre, int res_channels, float* out, void* stream) {
-  if (int rc = check_res_args("bcp_norm_eval_res", 1, rows, C, res_pre, res_channels)) return rc;
+  NormProblem p;
+  if (int rc = res_problem("bcp_norm_eval_res", 1, rows, C, nullptr, 0, act, res_pre, res_channels, p)) return rc;
   BCP_REQUIRE(y && running_mean && running_var && out, "bcp_norm_eval_res: null pointer");
   BCP_REQUIRE(aligned16(y) && aligned16(out) && aligned16(running_mean) && aligned16(running_var) && (!gamma || aligned16(gamma)) && (!beta || aligned16(beta)),
               "bcp_norm_eval_res: alignment");
   const long long nvec = rows * (C / 4);
   long long gx = (nvec + 255) / 256;
   if (gx > 4096) gx = 4096;
-  if (res_channels == 1)
-    hipLaunchKernelGGL((k_norm_eval_res<true>), dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, y, rows, C, gamma, beta, running_mean, running_var, eps, act, res_pre, out);
-  else
-    hipLaunchKernelGGL((k_norm_eval_res<false>), dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, y, rows, C, gamma, beta, running_mean, running_var, eps, act, res_pre, out);
+  hipLaunchKernelGGL(kEvalRes[res_channels == 1], dim3((unsigned)gx), dim3(256), 0, (hipStream_t)stream, y, rows, C, gamma, beta, running_mean, running_var, eps, act,
+                     res_pre, out);
   BCP_CHECK_LAUNCH("bcp_norm_eval_res");
   return BCP_OK;
 }
+

@@ -1,9 +1,53 @@
-// bcp_amd/csrc/norm_shared.h -- what csrc/norm.hip (BatchNorm / InstanceNorm) shares with csrc/gnorm.hip (GroupNorm): the reduction of the
-// per-block fp64 partial rows, and host launchers for the per-sample statistics / apply streams that GroupNorm runs unchanged (G = N).
+// bcp_amd/csrc/norm_shared.h -- what csrc/norm.hip (BatchNorm / InstanceNorm) shares with csrc/norm_res.hip (pre-activation residual) and
+// csrc/gnorm.hip (GroupNorm): the problem record of the family's host dispatch, the views of its two tables, the reduction of the
+// per-block fp64 partial rows, and host launchers for the finalize steps and the per-sample statistics / apply streams.
 #pragma once
 #include "common.h"
 
 namespace bcp {
+
+struct NormEpilogue {
+  const float* chan_scale;     // nullable [N][C]: Dropout3d keep*1/(1-p) per (sample, channel)
+  const uint8_t* elem_mask;    // nullable [rows][C]: elementwise Dropout keep mask
+  float elem_scale;            // 1/(1-p) for elem_mask
+  long long rows_per_sample;   // spatial size (rows per n) for chan_scale indexing
+  int act;
+  const unsigned long long* mask_seed;   // nullable (round 4): device seed of an elementwise Dropout whose keep bits are EVALUATED here
+  float p_keep;                          //   (bern_keep, common.h: the bits bcp_bernoulli_dev would write) instead of read from elem_mask
+};
+
+// ---- the problem record of the host dispatch (csrc/norm.hip norm_route() decides from it, norm_fwd_launch() / norm_bwd_launch() launch it).
+// Segments (see k_col_partial): the finer of (group, sample) when a per-sample channel scale is present -- spg of them per group
+constexpr int kMaxSamplesPerGroup = 64;      // (bcp_norm_workspace_bytes leaves room for this many more partial rows per group)
+struct NormProblem { int G; long long rows_per_group; int C; NormEpilogue ep; long long seg_rows; int spg; };
+// checks the extents, C (a power of two in 16 .. 1024) and that a group holds 1 .. kMaxSamplesPerGroup whole samples under a channel
+// scale; ep.rows_per_sample <= 0 stands for rows_per_group
+int norm_problem(const char* fn, int G, long long rows_per_group, int C, const NormEpilogue& ep, NormProblem& p);
+
+// the statistics table float[5][G][C] and the backward coefficients c1c2raw = float[4][G][C] (c1, c2, then the two raw sums)
+struct NormTable { float *mean, *rstd, *scale, *shift, *var_unb; };
+inline NormTable norm_table(const float* stats, int G, int C) {      // (the forward finalize steps are the only writers)
+  float* t = const_cast<float*>(stats);
+  return {t, t + (long long)G * C, t + 2LL * G * C, t + 3LL * G * C, t + 4LL * G * C};
+}
+struct NormCoef { float *c1, *c2, *raw; };
+inline NormCoef norm_coef(float* c1c2raw, int G, int C) { return {c1c2raw, c1c2raw + (long long)G * C, c1c2raw + 2LL * G * C}; }
+
+// ---- the route: everything the host decides about one call, decided once (csrc/norm.hip norm_route; launch-free and pure)
+enum class NormDir { Fwd, Bwd };
+enum class NormSrc { Tensor, Slabs, Partial };      // the statistics: a pass over the tensor, a pass that sums split-K slabs on its way in, rows handed in
+enum class NormForm { Own, Fused, Chain };          // one launch / statistics pass, apply pass that finalises / statistics pass, finalize, tail
+enum class NormTail { None, Apply, Params };        // behind the chain's finalize: the apply pass, or (no output) k_norm_running_only / k_norm_bwd_params
+struct NormRoute {
+  NormForm form; NormTail tail; bool stats, finalize;      // finalize: the finalize launch happens (stats: the statistics pass)
+  int nbps, nseg, nb;                                      // partial rows per segment, segments, partial rows per group
+  dim3 stat_grid, fin_grid, apply_grid, fused_grid, own_grid;
+  int GS, cw, P;                                           // the one-launch form: groups and channels per workgroup, kernel instance
+  bool skip_fin, skip_app, skip_bstat;                     // options().whatif: launches left out to price a change (wrong results)
+  int cap_rows; size_t c1_offset;                          // workspace: partial rows per group in front of c1c2raw, its byte offset
+};
+// has_out: an apply pass writes a tensor (the backward entry points: always); ordered: running statistics / parameter gradients are updated
+NormRoute norm_route(NormDir dir, NormSrc src, const NormProblem& p, bool has_out, bool ordered);
 
 // Sum the per-block partials of 16 channels of one group: 1024 threads = 32 doubles (16 channels x {s1, s2}, one 256-byte
 // row of the partial table) x 32 row-slots, four independent loads in flight per thread, then an LDS tree.  Threads 0..15

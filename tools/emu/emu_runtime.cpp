@@ -360,10 +360,12 @@ bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned
   std::lock_guard<std::mutex> lk(g_log_mu);
   g_log += "L|" + symbol_of(fn) + tail;
   if (values) g_log += "P|" + values->substr(0, values->empty() ? 0 : values->size() - 1) + "\n";      // (without the last comma)
-  return mode != 2 && mode != 3;
+  return mode < 2;
 }
 
-bool log_args() { return g_log_mode.load() == 3; }
+static std::atomic<uintptr_t> g_log_base{0};
+int log_args() { const int mode = g_log_mode.load(); return mode == 3 ? 1 : mode == 4 ? 2 : 0; }
+long long log_ptr_offset(const void* p) { return (long long)(reinterpret_cast<uintptr_t>(p) - g_log_base.load()); }
 
 void note_attr(const void* fn, int value) {
   if (g_log_mode.load() == 0) return;
@@ -375,7 +377,9 @@ void note_attr(const void* fn, int value) {
 
 // test-only exports (not part of the product library's ABI): set the log mode; copy the log out (NUL-terminated) and clear it.
 // bcpemu_log_take returns the bytes the whole log needs; with a smaller cap nothing is copied or cleared.
+// bcpemu_log_base: the address log mode 4 records pointer arguments against.
 extern "C" int bcpemu_log_mode(int mode) { return bcpemu::g_log_mode.exchange(mode); }
+extern "C" void bcpemu_log_base(const void* base) { bcpemu::g_log_base.store(reinterpret_cast<uintptr_t>(base)); }
 extern "C" long bcpemu_log_take(char* buf, long cap) {
   std::lock_guard<std::mutex> lk(bcpemu::g_log_mu);
   const long need = (long)bcpemu::g_log.size() + 1;

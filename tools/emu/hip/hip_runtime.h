@@ -63,14 +63,20 @@ enum hipFuncAttribute { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 // launch log (tests/test_emu_conv3_routes.py): mode 0 = off, 1 = note every launch and attribute call, 2 = note them and do not execute
 // the launches (entry points may then be handed any non-null aligned buffer), 3 = as 2 plus one "P|v,v,.." record behind each launch
 // record with the kernel's arguments of arithmetic type in order (tests/test_emu_gemm_routes.py; struct and pointer arguments are not
-// recorded).  Read through bcpemu_log_take (emu_runtime.cpp).
+// recorded), 4 = as 3 with each pointer argument recorded too: "null", or "@" and its byte offset from the address handed to
+// bcpemu_log_base (tests/test_emu_norm_routes.py: which buffer a launch reads, and where inside a workspace; struct arguments stay
+// unrecorded).  Read through bcpemu_log_take (emu_runtime.cpp).
 namespace bcpemu {
-// false: do not execute.  values (mode 3): the "P|" record's text, written with the "L|" record under one hold of the log's lock
+// false: do not execute.  values (modes 3, 4): the "P|" record's text, written with the "L|" record under one hold of the log's lock
 bool note_launch(const void* fn, unsigned gx, unsigned gy, unsigned gz, unsigned bx, unsigned by, unsigned bz, size_t shmem, const std::string* values = nullptr);
-bool log_args();                              // mode 3
-template <class T> inline void fmt_arg(std::string& s, const T& v) {
+int log_args();                               // 0; mode 3: 1; mode 4: 2 (pointers too)
+long long log_ptr_offset(const void* p);
+template <class T> inline void fmt_arg(std::string& s, const T& v, bool pointers) {
   if constexpr (std::is_integral<T>::value) s += std::to_string((long long)v) + ",";
   else if constexpr (std::is_floating_point<T>::value) { char b[40]; snprintf(b, sizeof b, "%.9g,", (double)v); s += b; }
+  else if constexpr (std::is_pointer<T>::value) {
+    if (pointers) s += v ? "@" + std::to_string(log_ptr_offset((const void*)v)) + "," : std::string("null,");
+  }
 }
 void note_attr(const void* fn, int value);
 }
@@ -324,8 +330,8 @@ using std::min;
 template <class K, class... Args>
 inline void bcpemu_launch(K kernel, dim3 grid, dim3 block, size_t shmem, hipStream_t, Args... args) {
   std::string values;
-  const bool with_args = ::bcpemu::log_args();
-  if (with_args) (::bcpemu::fmt_arg(values, args), ...);
+  const int with_args = ::bcpemu::log_args();
+  if (with_args) (::bcpemu::fmt_arg(values, args, with_args == 2), ...);
   if (!::bcpemu::note_launch((const void*)kernel, grid.x, grid.y, grid.z, block.x, block.y, block.z, shmem, with_args ? &values : nullptr)) return;
   std::function<void()> body = [=]() { kernel(args...); };
   ::bcpemu::run_grid(grid, block, shmem, body);
