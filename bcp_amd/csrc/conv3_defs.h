@@ -323,16 +323,40 @@ typedef _Float16 bcp_f16x2 __attribute__((ext_vector_type(2)));
 typedef float bcp_f32x2b __attribute__((ext_vector_type(2)));
 #endif
 
-// power of two s with amax * s in [2^13, 2^14); 1 for amax = 0 / NaN / Inf.  Exponent clamped to +-60 so that the product of an
-// activation scale and a weight scale (and its reciprocal) stays a normal fp32 number.
+//
+// GUARANTEED DOMAIN of the two-plane path (tests/wgrad_checks.py check_f16_range holds it, elementwise against fp64): every operand's
+// |max| in [2^-100, 2^100] -- each operand on its own, whatever the other one's |max| -- as long as the exact result is itself a normal
+// fp32 number.  There the path is as accurate as at |max| = 1 and finite data gives finite results.  The scale exponent is clamped to
+// +-120 (2^+-120 is a normal fp32 number; |max| from 2^-106 to 2^127 needs no clamp), and the two scales are undone on the accumulator
+// in TWO exact steps (F16Unscale below): their product 2^-(ea + eb) can leave the fp32 range (2^-50-sized activations times
+// 2^-50-sized gradients: 2^-128) where neither factor, nor the half-way value, nor the result does.  (With a clamp of +-60 and the
+// product as one factor, a |max| below 2^-60 lost its low bits or came back as zeros, and one above 2^74 as NaN from finite data.)
+// UNDEFINED for this path: an operand whose |max| is below 2^-100 (the clamp no longer lifts a |max| below 2^-106 into fp16's range,
+// and elements 2^-24 below such a maximum are fp32 subnormals) or above 2^100.  |max| = 0 / NaN / Inf: scale 1, and the result is what
+// the arithmetic gives -- zeros, or NaN exactly where the other paths give it (check_conv3_f16, check_wgrad_nonfinite).
+//
+// power of two s with amax * s in [2^13, 2^14); 1 for amax = 0 / NaN / Inf
 __host__ __device__ __forceinline__ int f16_scale_exp(float amax) {
   if (!(amax > 0.f) || !(amax < 3.0e38f)) return 0;
   int e;
   (void)frexpf(amax, &e);                  // amax = m * 2^e, m in [0.5, 1)
   e = 14 - e;
-  return e > 60 ? 60 : (e < -60 ? -60 : e);
+  return e > 120 ? 120 : (e < -120 ? -120 : e);
 }
 __host__ __device__ __forceinline__ float f16_scale(float amax) { return ldexpf(1.f, f16_scale_exp(amax)); }
+
+// 2^-(ea + eb), what undoes two operand scales on an accumulator, as two powers of two of half the exponent each: acc * u multiplies by
+// one, then by the other.  Both are normal numbers (|exponent| <= 120) and the value in between lies between acc and the result, so the
+// only rounding is the one the result itself needs; where the single factor was a normal number (|ea + eb| <= 126) the bits are those
+// of acc * 2^-(ea + eb).  The default {1, 1} is an exact no-op (three bf16 planes).
+struct F16Unscale { float a = 1.f, b = 1.f; };
+__host__ __device__ __forceinline__ F16Unscale f16_unscale(int ea, int eb) {
+  const int t = -(ea + eb), h = t / 2;
+  F16Unscale u;
+  u.a = ldexpf(1.f, h); u.b = ldexpf(1.f, t - h);
+  return u;
+}
+__host__ __device__ __forceinline__ float operator*(float acc, const F16Unscale& u) { return acc * u.a * u.b; }
 
 // two floats -> packed fp16 pair (low half = a), round to nearest even (v_cvt_pk_f16_f32 on gfx950)
 __device__ __forceinline__ unsigned cvt_pk_f16(float a, float b) {

@@ -110,7 +110,7 @@ template <class TL, int TD, int TH, int TW, int NT, int MTv = TL::MT, bool BW = 
 __device__ __forceinline__ void b6_store_tile(f32x4 (&acc)[MTv][NT], float* __restrict__ Y, const float* __restrict__ bias, const ConvDims& cd,
                                               int n, int d0, int h0, int w0, int cout0, int accumulate, bool want_stats,
                                               double (&s1)[NT][4], double (&s2)[NT][4], int wv = -1, const StatsArg* sb = nullptr, int gg = 0,
-                                              float osc = 1.f /* power of two undoing the fp16 pre-scales (PL = 2); 1: exact no-op */) {
+                                              F16Unscale osc = {} /* undoes the fp16 pre-scales (PL = 2); default: exact no-op */) {
   constexpr int MT = MTv, CT = NT * 16;
   const int lane = threadIdx.x & 63, wave = wv >= 0 ? wv : (int)(threadIdx.x >> 6);
   const int li = lane & 15, lg = lane >> 4;
@@ -215,7 +215,7 @@ __device__ __forceinline__ void b6_store_tile(f32x4 (&acc)[MTv][NT], float* __re
 template <class TL, int TD, int TH, int TW, int NT, bool BW = false>
 __device__ __forceinline__ void b6_epilogue(f32x4 (&acc)[TL::MT][NT], float* __restrict__ Y, const float* __restrict__ bias, const ConvDims& cd,
                                             int n, int d0, int h0, int w0, int cout0, int accumulate, const StatsArg& st, double* Ss, int bx,
-                                            float osc = 1.f) {
+                                            F16Unscale osc = {}) {
   double s1[NT][4], s2[NT][4];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt)
@@ -280,11 +280,12 @@ __global__ __launch_bounds__(256) void k_c3b(const float* __restrict__ X, const 
   // stage `sg` of chunk `cc`: tap pairs sg*SP .. sg*SP+SP-1 of the pre-split pack Wb16[chunk][pair][piece][Cout16][32] (bf16, behind the
   // fp32 pack: bcp_conv3_packed_weight_floats); 16-byte piece q of the stage = (pair, piece, cout, k quarter)
   const unsigned short* Wb16 = reinterpret_cast<const unsigned short*>(Wp + PP::pack_off(T, cd.Cin16, cd.Cout16));
-  float xsc = 1.f, osc = 1.f;          // PL = 2: power-of-two pre-scales (k_c3d)
+  float xsc = 1.f;
+  F16Unscale osc;          // PL = 2: power-of-two pre-scales (k_c3d)
   if (PL == 2) {
     const int ex = f16_scale_exp(amax_read(cd.xamax)), ew = f16_scale_exp(Wp[pack_off_hdr(T, cd.Cin16, cd.Cout16)]);
     xsc = ldexpf(1.f, ex);
-    osc = ldexpf(1.f, -(ex + ew));
+    osc = f16_unscale(ex, ew);
   }
   // (branch-free: every thread loads -- slots past the stage re-read its first pieces, pairs past TP re-read the last pair -- and
   //  wstash drops / zeroes what is not wanted; a predicated load would cost a vmcnt(0) per stage, see fetch_nb)
@@ -714,11 +715,12 @@ __global__ __launch_bounds__(256) void k_c3p(const float* __restrict__ X, const 
 #pragma unroll
     for (int u = 0; u < 3; ++u) wq[u] = (unsigned)((((u < PL ? u : 0) * cd.Cout16 + cout0 + co) * 32 + kq * 8) * 2);
   }
-  float xsc = 1.f, osc = 1.f;          // PL = 2: power-of-two pre-scales (k_c3d)
+  float xsc = 1.f;
+  F16Unscale osc;          // PL = 2: power-of-two pre-scales (k_c3d)
   if (PL == 2) {
     const int ex = f16_scale_exp(amax_read(cd.xamax)), ew = f16_scale_exp(Wp[pack_off_hdr(T, cd.Cin16, cd.Cout16)]);
     xsc = ldexpf(1.f, ex);
-    osc = ldexpf(1.f, -(ex + ew));
+    osc = f16_unscale(ex, ew);
   }
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   char* const Wr_wave = reinterpret_cast<char*>(Wr) + wave_u * 1024;        // this wave's 1 KB of every plane
@@ -975,11 +977,12 @@ __global__ __launch_bounds__(256) BCP_C3D_ATTR void k_c3d(const float* __restric
 
   // PL = 2: power-of-two pre-scale of the activations (their |max| from the norm apply pass that wrote them) and of the weights
   // (pack header); osc undoes both on the accumulators
-  float xsc = 1.f, osc = 1.f;
+  float xsc = 1.f;
+  F16Unscale osc;
   if (PL == 2) {
     const int ex = f16_scale_exp(amax_read(cd.xamax)), ew = f16_scale_exp(Wp[pack_off_hdr(T, cd.Cin16, cd.Cout16)]);
     xsc = ldexpf(1.f, ex);
-    osc = ldexpf(1.f, -(ex + ew));
+    osc = f16_unscale(ex, ew);
   }
   // lane (li, lg): output channel li of n-tile nt, k quarter lg of pre-split pack row [chunk][pair][piece][cout][32 k]
   const unsigned short* Wl = reinterpret_cast<const unsigned short*>(Wp + PP::pack_off(T, cd.Cin16, cd.Cout16)) + (long long)(cout0 + li) * 32 + lg * 8;
@@ -1523,11 +1526,12 @@ __global__ __launch_bounds__(256) void k_c3q(const float* __restrict__ X, const 
   // DMA instruction u of wave w carries pieces (u * 256 + w * 64) % NPIECE + lane (instructions past the stage repeat its first
   // pieces: same bytes to the same place); piece q = (plane q / (4 CT), row (q >> 2) % CT, k quarter POSITION q & 3) at byte 16 q
   const char* Wb16 = reinterpret_cast<const char*>(Wp + PP::pack_off(T, cd.Cin16, cd.Cout16));
-  float xsc = 1.f, osc = 1.f;          // PL = 2: power-of-two pre-scales (k_c3d)
+  float xsc = 1.f;
+  F16Unscale osc;          // PL = 2: power-of-two pre-scales (k_c3d)
   if (PL == 2) {
     const int ex = f16_scale_exp(amax_read(cd.xamax)), ew = f16_scale_exp(Wp[pack_off_hdr(T, cd.Cin16, cd.Cout16)]);
     xsc = ldexpf(1.f, ex);
-    osc = ldexpf(1.f, -(ex + ew));
+    osc = f16_unscale(ex, ew);
   }
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   static_assert(NDMA <= 3, "k_c3q: at most 64-channel slabs");

@@ -97,10 +97,11 @@ __global__ __launch_bounds__(256) void k_w6(const float* __restrict__ X, const f
   HIP_DYNAMIC_SHARED(float4, smem4)
   unsigned short* Xb = reinterpret_cast<unsigned short*>(smem4);   // [PL][HV][16]
   unsigned short* Yb = Xb + PL * XPLANE;                           // [PL][M][YS]
-  float xsc = 1.f, ysc = 1.f, osc = 1.f;
+  float xsc = 1.f, ysc = 1.f;
+  F16Unscale osc;
   if (PL == 2) {
     const int ex = f16_scale_exp(amax_read(cd.xamax)), ey = f16_scale_exp(amax_read(cd.yamax));
-    xsc = ldexpf(1.f, ex); ysc = ldexpf(1.f, ey); osc = ldexpf(1.f, -(ex + ey));
+    xsc = ldexpf(1.f, ex); ysc = ldexpf(1.f, ey); osc = f16_unscale(ex, ey);
   }
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -1326,8 +1326,8 @@ def check_conv3_f16(ops, dev):
     pre-scales from the input's |max| -- x_amax -- and the layer's weights' |max| in the pack header).  The gate VERDICT r03 item 4 sets:
     error against an fp64 convolution <= 3x the fp32-MFMA kernel's on the same data, on the in-step kinds of shapes AND on inputs / weights
     whose magnitudes span 1e-4 .. 1e3 (uniformly small, uniformly large, mixed per element); the path must really be the fp16 one (bits
-    differ from the three-plane result), an amax that is only an upper bound must do, zero / NaN inputs behave as on the other paths; fused
-    statistics, +=, dgrad pack, persistent tiles.  Also: the norm apply pass leaves exactly max |a| for its consumer."""
+    differ from the three-plane result), an amax that is only an upper bound must do, zero / NaN inputs behave as on the other paths (the weight
+    gradient's too: wgrad_checks.check_wgrad_nonfinite); fused statistics, +=, dgrad pack, persistent tiles.  Also: the norm apply pass leaves exactly max |a| for its consumer."""
     rng = np.random.default_rng(404)
     cases = (  # N, Cin, Cout, spatial, KD, conv3_b6 level needed, conv3_p
         (1, 32, 32, (8, 16, 16), 3, 2, None),        # k_c3d 4x8x8 x 32 (LA level 2)
